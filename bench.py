@@ -4,18 +4,23 @@ Default workload (BASELINE configs[1], C2): 'balance', 32 768 envs per GPU, n_ag
 10 physics substeps, continuous random actions U(-1, 1).  One process per GPU (weak scaling:
 every rank simulates its own 32 768 independent envs, no data-path collective).
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
-Prints ONE JSON line (rank 0) with the driver's contract fields plus:
+A plain run sets up, warms up, times the K steps and prints ONE JSON line (rank 0) with the
+driver's contract fields (``value`` env-steps/s, ``ms_per_step`` of one timed step, ...).
+``--dump-outputs DIR`` also writes what the last timed step returned (observations, rewards,
+dones, infos) as ``DIR/<name>.npy``.  With N > 1 the line also holds
+  process_group -- the live group: backend, world size, per-rank rates and each rank's
+                   device identity (PCI address / UUID of its GPU)
+``--full`` adds, from runs of their own after the timed region (and with the step kernel's own
+timers switched on):
   roofline      -- HBM roofline of the dominant kernel (k_world, the world-specialised step
                    kernel; k_step on worlds it cannot specialise): algorithmic bytes per env-step
                    from SURVEY.md §8d (24*E_all + 24*E_dyn + 12*A) over its time per
                    launch, HIP events on the stream it runs on; `frac` is the variant the timed
                    steps run (with the scenario program as its epilogue when the replay fuses it),
-                   `plain` the step kernel alone
-  process_group -- (N > 1) the live group: backend, world size, per-rank rates and each rank's
-                   device identity (PCI address / UUID of its GPU)
+                   `plain` the step kernel alone; roofline_program: the scenario program's
   cpu_baseline  -- the CPU oracle (PyTorch restatement of the reference tensor program) driving
                    the same host layer, timed on this host on a bounded sample (rank 0, N=1)
 """
@@ -52,11 +57,18 @@ def parse():
                    help="physics substeps; default: the scenario's §8(d) config (balance C2: 10), else the "
                         "scenario's own World(substeps=...); 0 = the scenario's own")
     p.add_argument("--broadphase", default="batch", choices=["batch", "env"])
-    p.add_argument("--cpu-steps", type=int, default=2, help="timed CPU-oracle steps per repeat (0 = skip)")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also measure the kernel rooflines (timers of their own) and the "
+                        "CPU-oracle baseline; a plain run only times the steps")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="write what the last timed step returned (observations, rewards, dones, infos) as "
+                        "DIR/<name>.npy (float32, under 64 MB in all: a fixed seeded sample of the envs where needed)")
+    p.add_argument("--cpu-steps", type=int, default=2,
+                   help="--full: timed CPU-oracle steps per repeat (0 = skip)")
     p.add_argument("--cpu-repeats", type=int, default=5, help="CPU-oracle repeats (the median is reported)")
     p.add_argument("--cpu-envs", type=int, default=32768)
     p.add_argument("--event-launches", type=int, default=20,
-                   help="extra eager step launches timed with HIP events after the timed region")
+                   help="--full: extra eager step launches timed with HIP events after the timed region")
     p.add_argument("--device", default=None, help="override device (e.g. cpu for plumbing tests)")
     p.add_argument("--graph", default="auto", choices=["auto", "on", "off"],
                    help="auto: make_env without graph_step, the reference API's call (the package's "
@@ -354,6 +366,52 @@ def cpu_baseline(args):
     }
 
 
+DUMP_MAX_BYTES = 60_000_000  # (the arrays; with the .npy headers the files stay under 64 MB)
+
+
+def _named_outputs(name: str, v, out: dict) -> None:
+    """Flatten a step's return value (tensors in lists / dicts, by index / key) into {name: tensor}."""
+    if isinstance(v, torch.Tensor):
+        out["".join(c if c.isalnum() else "_" for c in name)] = v
+    elif isinstance(v, dict):
+        for k, x in v.items():
+            _named_outputs(f"{name}_{k}", x, out)
+    elif isinstance(v, (list, tuple)):
+        for i, x in enumerate(v):
+            _named_outputs(f"{name}_{i}", x, out)
+
+
+def dump_outputs(result, num_envs: int, directory: str, rank: int = 0) -> dict:
+    """``--dump-outputs``: what the last timed ``env.step`` returned, one ``<name>.npy`` per tensor
+    (obs_<agent>, rewards_<agent>, dones, infos_<agent>_<key>; float32, float64 kept).  Above
+    DUMP_MAX_BYTES in all, the same fixed sample of envs (seeded, sorted) is taken of every
+    per-env tensor.  Returns {name: shape} of what was written."""
+    import numpy as np
+
+    names = ("obs", "rewards", "dones", "infos") if len(result) == 4 else (
+        "obs", "rewards", "terminated", "truncated", "infos")
+    tensors: dict = {}
+    for n, v in zip(names, result):
+        _named_outputs(n if rank == 0 else f"rank{rank}_{n}", v, tensors)
+    arrays = {}
+    for n, t in tensors.items():
+        a = t.detach().cpu().numpy()
+        arrays[n] = a if a.dtype == np.float64 else a.astype(np.float32)
+    per_env = {n for n, a in arrays.items() if a.ndim >= 1 and a.shape[0] == num_envs}
+    fixed = sum(a.nbytes for n, a in arrays.items() if n not in per_env)
+    row = sum(arrays[n].nbytes // num_envs for n in per_env)
+    if fixed + row * num_envs > DUMP_MAX_BYTES:
+        keep = max(1, (DUMP_MAX_BYTES - fixed) // max(row, 1))
+        idx = np.sort(np.random.default_rng(0).choice(num_envs, size=keep, replace=False))
+        for n in per_env:
+            arrays[n] = arrays[n][idx]
+    d = Path(directory)
+    d.mkdir(parents=True, exist_ok=True)
+    for n, a in arrays.items():
+        np.save(d / f"{n}.npy", np.ascontiguousarray(a))
+    return {n: list(a.shape) for n, a in arrays.items()}
+
+
 def device_identity(device: str, rank: int, local_rank: int) -> dict:
     """Which device this rank ran on, as the rank itself sees it: the PCI address and UUID of its
     GPU (torch.cuda.get_device_properties), the visible-device lists it was started with, its host
@@ -438,11 +496,14 @@ def main():
             else:
                 dist.barrier()
 
-    if on_gpu:
+    # --full: the step kernel's own timers (for the rooflines) and the timers / baselines that take
+    # runs of their own after the timed region; a plain run only times the steps
+    full = args.full
+    if on_gpu and full:
         world.engine.set_timing(True)
     for _ in range(args.warmup):
         env.step(env.get_random_actions())
-    if on_gpu:
+    if on_gpu and full:
         world.engine.get_timing(reset=True)
         world.engine.device_timing(reset=True)
     sync()
@@ -451,12 +512,14 @@ def main():
     handovers = type(env.scenario).make_world.__globals__.get("HANDOVERS", [0])  # (discovery's respawn)
     h0 = handovers[0]
     tails0 = _tail_launches() if on_gpu else 0
-    ev_region = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) if on_gpu else None
+    ev_region = ((torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+                 if on_gpu and full else None)
     if ev_region:
         ev_region[0].record()
+    last = None
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        env.step(env.get_random_actions())
+        last = env.step(env.get_random_actions())
     if ev_region:
         ev_region[1].record()
     sync()
@@ -464,6 +527,10 @@ def main():
     sync()
     elapsed = time.perf_counter() - t0
     tails = (_tail_launches() - tails0) if on_gpu else 0
+    dumped = None
+    if args.dump_outputs and last is not None:
+        # (before anything else is launched: a graph step returns its own output buffers)
+        dumped = dump_outputs(last, args.envs, args.dump_outputs, rank)
     # the GPU time of the timed region itself (HIP events on the step stream around the loop); per
     # launch when every step was exactly one launch (a one-launch kernel chain that also ran the
     # post-replay work as its tail: nothing else is queued per step)
@@ -471,15 +538,16 @@ def main():
     gch = getattr(getattr(env, "_graph", None), "_chain", None)
     one_launch = bool(on_gpu and env.graph_status == "graph" and gch is not None and gch.n_nodes == 1
                       and tails == args.steps)
+    gpu_full = on_gpu and full
     kernel_ms, launches, timer, clock_ghz = 0.0, 0, None, 0.0
     event_us = fused_us = None
-    if on_gpu:
+    if gpu_full:
         # (the timed region's own launches: read before the fused timer's launches add to the count)
         dev_ms, dev_n, clock_ghz = world.engine.device_timing(reset=True, with_clock=True)
-    if on_gpu and args.event_launches > 0 and env.graph_status == "graph":
+    if gpu_full and args.event_launches > 0 and env.graph_status == "graph":
         # (first launches after the timed region: tools/rocprof_record.py finds these 5 + 50 there)
         fused_us = time_fused_chain(env)
-    if on_gpu:
+    if gpu_full:
         if env.graph_status == "graph":
             # replayed launches: HIP records no events inside a graph; the kernel's own timer
             kernel_ms, launches = dev_ms, dev_n
@@ -498,7 +566,7 @@ def main():
             ev_ms, ev_n = world.engine.get_timing(reset=True)
             event_us = 1e3 * ev_ms / ev_n if ev_n else None
     program = None
-    if on_gpu and args.event_launches > 0:
+    if gpu_full and args.event_launches > 0:
         prog_ms, prog_timer = time_program(env, args.event_launches)
         p_env = program_bytes_per_env_step(env)
         ach = p_env * args.envs / (prog_ms * 1e-3) / 1e9
@@ -512,7 +580,7 @@ def main():
         }
     group = None
     graph_us = None
-    if on_gpu and args.event_launches > 0 and env.graph_status == "graph":
+    if gpu_full and args.event_launches > 0 and env.graph_status == "graph":
         try:
             graph_us, graph_n = time_step_kernel_graph(world)
         except Exception as exc:  # noqa: BLE001 -- the eager events stay the headline then
@@ -690,6 +758,7 @@ def main():
         "n_gpus": world_size,
         "steps": args.steps,
         "warmup": args.warmup,
+        "full": full,
         "ms_per_step": round(1e3 * elapsed / args.steps, 4),
         "higher_is_better": True,
         "scaling": "weak",
@@ -710,6 +779,8 @@ def main():
         "roofline": roofline,
         "roofline_program": program,
     }
+    if dumped is not None:
+        out["outputs"] = {"dir": str(args.dump_outputs), "arrays": dumped}
     if group is not None:
         out["process_group"] = group
     if args.scenario == "discovery":  # (one-launch respawns redone: by the per-target kernels or the reference loop)
@@ -718,7 +789,7 @@ def main():
             "timed": handovers[0] - h0, "total": handovers[0],
             "to_reference_loop": g_.get("REFERENCE_LOOP", [None])[0],
             "why": g_.get("HANDOVER_LOG", [])}
-    if rank == 0 and world_size == 1 and args.cpu_steps > 0:
+    if rank == 0 and world_size == 1 and full and args.cpu_steps > 0:
         out["cpu_baseline"] = cpu_baseline(args)
     if rank == 0:
         print(json.dumps(out), flush=True)

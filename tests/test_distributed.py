@@ -68,6 +68,74 @@ def test_bench_world_size_mismatch_fails():
     assert out.returncode != 0 and "WORLD_SIZE" in out.stderr
 
 
+def _run_bench(argv, capsys):
+    sys.path.insert(0, str(ROOT))
+    import bench
+
+    old = sys.argv
+    try:
+        sys.argv = ["bench.py", *argv]
+        bench.main()
+    finally:
+        sys.argv = old
+    lines = [l for l in capsys.readouterr().out.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, lines
+    return json.loads(lines[0])
+
+
+def test_bench_plain_run_dumps_its_outputs(tmp_path, capsys):
+    """A plain run times the steps and nothing else; --dump-outputs writes what the last timed step
+    returned, the same arrays from the same arguments."""
+    import numpy as np
+
+    base = ["--gpus", "1", "--steps", "3", "--warmup", "1", "--envs", "64", "--device", "cpu"]
+    recs = [_run_bench(base + ["--dump-outputs", str(tmp_path / d)], capsys) for d in ("a", "b")]
+    rec = recs[0]
+    assert rec["steps"] == 3 and rec["full"] is False
+    assert rec["ms_per_step"] > 0 and abs(rec["value"] * rec["ms_per_step"] * 1e-3 / 64 - 1) < 1e-2
+    assert "cpu_baseline" not in rec and rec["roofline"] is None and rec["roofline_program"] is None
+    a = {f.name: np.load(f) for f in sorted((tmp_path / "a").glob("*.npy"))}
+    b = {f.name: np.load(f) for f in sorted((tmp_path / "b").glob("*.npy"))}
+    assert set(a) == set(b) == {n + ".npy" for n in rec["outputs"]["arrays"]}
+    assert {"dones.npy", "obs_0.npy", "obs_3.npy", "rewards_0.npy", "rewards_3.npy"} <= set(a)
+    for n in a:
+        assert a[n].dtype in (np.float32, np.float64) and a[n].shape[0] == 64, n
+        assert np.isfinite(a[n]).all() and np.array_equal(a[n], b[n]), n
+    assert a["obs_0.npy"].ndim == 2 and np.abs(a["obs_0.npy"]).max() > 0
+    assert sum(x.nbytes for x in a.values()) <= 64 << 20
+
+
+def test_bench_dump_samples_large_outputs(tmp_path, monkeypatch):
+    """Above the size limit every per-env array keeps the same fixed sample of envs."""
+    import numpy as np
+    import torch
+
+    sys.path.insert(0, str(ROOT))
+    import bench
+
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 4096)
+    obs = [torch.arange(300 * 5, dtype=torch.float32).reshape(300, 5) for _ in range(2)]
+    rews = [torch.arange(300, dtype=torch.float32) for _ in range(2)]
+    dones = torch.arange(300) % 2 == 0
+    shapes = [bench.dump_outputs([obs, rews, dones, [{}, {}]], 300, str(tmp_path / d)) for d in ("a", "b")]
+    assert shapes[0] == shapes[1]
+    a = {f.stem: np.load(f) for f in (tmp_path / "a").glob("*.npy")}
+    assert set(a) == {"obs_0", "obs_1", "rewards_0", "rewards_1", "dones"}
+    rows = a["rewards_0"].astype(int)
+    assert 1 < len(rows) < 300 and (np.diff(rows) > 0).all()
+    assert sum(x.nbytes for x in a.values()) <= 4096
+    assert np.array_equal(a["obs_0"][:, 0], 5.0 * rows) and np.array_equal(a["dones"], (rows % 2 == 0).astype(np.float32))
+    for n, x in a.items():
+        assert np.array_equal(x, np.load(tmp_path / "b" / f"{n}.npy")), n
+
+
+def test_bench_full_adds_the_cpu_baseline(capsys):
+    rec = _run_bench(["--gpus", "1", "--steps", "2", "--warmup", "1", "--envs", "64", "--device", "cpu", "--full",
+                      "--cpu-steps", "1", "--cpu-repeats", "1", "--cpu-envs", "64"], capsys)
+    assert rec["full"] is True and rec["steps"] == 2 and rec["ms_per_step"] > 0
+    assert rec["cpu_baseline"]["value"] > 0 and rec["cpu_baseline"]["substeps1"]["value"] > 0
+
+
 def test_bench_presets():
     """C5 needs no extra flags: flocking's own substeps (ref flocking.py:36: substeps=5), not C2's 10."""
     sys.path.insert(0, str(ROOT))

@@ -8,6 +8,7 @@ kernel's launches as the bench ran them: `avg_us` = the last 50 launches, the be
 timer (World.step() replayed back to back, the step kernel alone); `in_step_us` = the launches of
 the timed steps (in a fused replay k_world also runs the scenario program as its epilogue);
 `avg_all_us` = every launch.  Without the trace, `avg_us` is the stats' average over every launch.
+The profiled command is a `bench.py --full` run (the roofline and its timers' launches).
 usage: python tools/rocprof_record.py <kernel_stats.csv> <bench log holding the JSON line> [summary path]
 """
 import csv

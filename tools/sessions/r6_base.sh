@@ -11,6 +11,6 @@ step() {
     echo "=== $name rc=$rc"; tail -n 4 "$OUT/$name.log" | cut -c1-600
     case $rc in 0) ;; *) echo "fatal rc=$rc, stopping"; exit $rc;; esac
 }
-step bench_c2 600 python bench.py
-step prof_c2 600 rocprofv3 --kernel-trace --stats -d $OUT/prof -o run -- python bench.py --cpu-steps 0
+step bench_c2 600 python bench.py --full
+step prof_c2 600 rocprofv3 --kernel-trace --stats -d $OUT/prof -o run -- python bench.py --full --cpu-steps 0
 echo "session done"

@@ -18,15 +18,15 @@ PART=${1:-all}  # A: smoke, suite, bench lines; B: rocprof + PMC (gpurun caps on
 if [ "$PART" != B ]; then
 step smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
 step pytest_gpu 1100 python -u -m pytest tests -m gpu -v -p no:cacheprovider --timeout 300 --timeout-method thread
-step bench_c2 600 python bench.py
-step bench_c3 600 python bench.py --scenario transport --cpu-steps 0
-step bench_c4 600 python bench.py --scenario discovery --cpu-steps 0
-step bench_c5 600 python bench.py --scenario flocking --cpu-steps 0
-step bench_c5full 600 python bench.py --scenario flocking --envs 262144 --steps 30 --warmup 10 --cpu-steps 0
-step bench_c2_eager 600 python bench.py --graph off --cpu-steps 0
+step bench_c2 600 python bench.py --full
+step bench_c3 600 python bench.py --full --scenario transport --cpu-steps 0
+step bench_c4 600 python bench.py --full --scenario discovery --cpu-steps 0
+step bench_c5 600 python bench.py --full --scenario flocking --cpu-steps 0
+step bench_c5full 600 python bench.py --full --scenario flocking --envs 262144 --steps 30 --warmup 10 --cpu-steps 0
+step bench_c2_eager 600 python bench.py --full --graph off --cpu-steps 0
 fi
 if [ "$PART" != A ]; then
-step prof_c2 600 rocprofv3 --kernel-trace --stats -d $OUT/prof -o run --output-format csv -- python bench.py --cpu-steps 0
+step prof_c2 600 rocprofv3 --kernel-trace --stats -d $OUT/prof -o run --output-format csv -- python bench.py --full --cpu-steps 0
 TAG=${PMC_TAG:-r6final} BENCH_ARGS="--steps 10 --warmup 10 --cpu-steps 0" bash tools/pmc_session.sh || exit $?
 fi
 echo "session done"

@@ -13,5 +13,5 @@ step() {
 }
 step smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
 step pytest_gpu 1000 python -u -m pytest tests -m gpu -q -p no:cacheprovider --timeout 300 --timeout-method thread
-step bench_c2 600 python bench.py
+step bench_c2 600 python bench.py --full
 echo "session done"

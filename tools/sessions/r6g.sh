@@ -14,7 +14,7 @@ step() {
     case $rc in 124|134|137|139) echo "fatal rc=$rc, stopping"; exit $rc;; esac
 }
 step pytest 900 python -u -m pytest tests/test_graph.py tests/test_spawn.py -m gpu -v -p no:cacheprovider --timeout 300 --timeout-method thread
-step bench_c2_recheck 600 python bench.py
-step bench_c5 600 python bench.py --scenario flocking --cpu-steps 0
-step bench_c5full 600 python bench.py --scenario flocking --envs 262144 --steps 30 --warmup 10 --cpu-steps 0
+step bench_c2_recheck 600 python bench.py --full
+step bench_c5 600 python bench.py --full --scenario flocking --cpu-steps 0
+step bench_c5full 600 python bench.py --full --scenario flocking --envs 262144 --steps 30 --warmup 10 --cpu-steps 0
 echo "session done"

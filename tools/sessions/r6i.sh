@@ -9,11 +9,11 @@ tail -3 $OUT/pytest.log; [ $rc -eq 0 ] || { echo "pytest rc=$rc"; grep -E "^(FAI
 summ() { tail -1 "$1" | python -c "import json,sys; d=json.loads(sys.stdin.read()); r=d['roofline']; print('$2', round(d['value']/1e6,1), d['ms_per_step'], r['kernel_us_per_launch'], r.get('kernel_us_timed_region'))"; }
 for i in 1 2; do
   for v in 1 0; do
-    VMAS_GRAPH_TAIL=$v timeout -k 10 300 python bench.py --cpu-steps 0 > $OUT/bench_c2_tail${v}_$i.log 2>&1 || { echo "bench rc=$?"; exit 1; }
+    VMAS_GRAPH_TAIL=$v timeout -k 10 300 python bench.py --full --cpu-steps 0 > $OUT/bench_c2_tail${v}_$i.log 2>&1 || { echo "bench rc=$?"; exit 1; }
     summ $OUT/bench_c2_tail${v}_$i.log "c2 tail=$v"
-    VMAS_GRAPH_TAIL=$v timeout -k 10 300 python bench.py --scenario transport --cpu-steps 0 > $OUT/bench_c3_tail${v}_$i.log 2>&1 || { echo "bench rc=$?"; exit 1; }
+    VMAS_GRAPH_TAIL=$v timeout -k 10 300 python bench.py --full --scenario transport --cpu-steps 0 > $OUT/bench_c3_tail${v}_$i.log 2>&1 || { echo "bench rc=$?"; exit 1; }
     summ $OUT/bench_c3_tail${v}_$i.log "c3 tail=$v"
   done
 done
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/prof -o run --output-format csv -- python bench.py --cpu-steps 0 --steps 40 > $OUT/prof.log 2>&1 || { echo "prof rc=$?"; exit 1; }
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/prof -o run --output-format csv -- python bench.py --full --cpu-steps 0 --steps 40 > $OUT/prof.log 2>&1 || { echo "prof rc=$?"; exit 1; }
 echo "session done"

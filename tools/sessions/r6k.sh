@@ -5,7 +5,7 @@ set -u
 OUT=${OUT:-gpurun_out/r6k}; mkdir -p $OUT
 export TMPDIR=/tmp
 for v in full nocopy nodraw; do
-  VMAS_TAIL_DIAG=$v timeout -k 10 300 rocprofv3 --kernel-trace -d $OUT/prof_$v -o run --output-format csv -- python bench.py --cpu-steps 0 --steps 40 --event-launches 0 > $OUT/prof_$v.log 2>&1 || { echo "prof rc=$?"; exit 1; }
+  VMAS_TAIL_DIAG=$v timeout -k 10 300 rocprofv3 --kernel-trace -d $OUT/prof_$v -o run --output-format csv -- python bench.py --full --cpu-steps 0 --steps 40 --event-launches 0 > $OUT/prof_$v.log 2>&1 || { echo "prof rc=$?"; exit 1; }
   python - "$OUT/prof_$v" "$v" <<'PY'
 import csv, glob, statistics as st, sys
 f = glob.glob(sys.argv[1] + "/**/run_kernel_trace.csv", recursive=True)[0]

@@ -5,13 +5,13 @@ set -u
 OUT=${OUT:-gpurun_out/r6l}; mkdir -p $OUT
 export TMPDIR=/tmp
 ARGS="--scenario flocking --cpu-steps 0 --steps 30 --warmup 10 --event-launches 0"
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/prof -o run --output-format csv -- python bench.py $ARGS > $OUT/prof.log 2>&1 || { echo "prof rc=$?"; exit 1; }
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/prof -o run --output-format csv -- python bench.py --full $ARGS > $OUT/prof.log 2>&1 || { echo "prof rc=$?"; exit 1; }
 tail -1 $OUT/prof.log | cut -c1-160
 f=$(find $OUT/prof -name 'run_kernel_stats.csv' | head -1); cut -d, -f1-4 "$f" | cut -c1-150
 i=0
 for counters in "FETCH_SIZE SQ_WAVES SQ_INSTS_VALU SQ_INSTS_VMEM SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_LDS" "WRITE_SIZE SQ_BUSY_CYCLES SQ_INSTS_SALU SQ_LDS_BANK_CONFLICT GRBM_GUI_ACTIVE"; do
   i=$((i+1))
-  timeout -k 10 120 rocprofv3 --pmc $counters --kernel-include-regex "k_flocking_fast" -d $OUT/p$i -o pmc --output-format csv -- python bench.py $ARGS > $OUT/p$i.log 2>&1
+  timeout -k 10 120 rocprofv3 --pmc $counters --kernel-include-regex "k_flocking_fast" -d $OUT/p$i -o pmc --output-format csv -- python bench.py --full $ARGS > $OUT/p$i.log 2>&1
   rc=$?; echo "pass $i rc=$rc"
   case $rc in 0|1|2) ;; *) exit $rc;; esac
   python - "$OUT/p$i" <<'PY'

@@ -9,12 +9,12 @@ timeout -k 10 400 python -u -m pytest tests/test_fused.py -m gpu -q -p no:cachep
 tail -1 $OUT/pytest.log
 for i in 1 2 3; do
   for s in 0 1; do
-    VMAS_FLOCK_SPLIT=$s timeout -k 10 200 python bench.py --scenario flocking --cpu-steps 0 --steps 200 > $OUT/c5_${s}_$i.log 2>&1 || { echo "bench rc=$?"; exit 1; }
+    VMAS_FLOCK_SPLIT=$s timeout -k 10 200 python bench.py --full --scenario flocking --cpu-steps 0 --steps 200 > $OUT/c5_${s}_$i.log 2>&1 || { echo "bench rc=$?"; exit 1; }
     echo "split=$s $(grep -o '"value": [0-9.]*' $OUT/c5_${s}_$i.log) $(grep -o '"ms_per_step": [0-9.]*' $OUT/c5_${s}_$i.log)"
   done
 done
 for s in 0 1; do
-  VMAS_FLOCK_SPLIT=$s timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/prof_$s -o run --output-format csv -- python bench.py --scenario flocking --cpu-steps 0 --steps 30 --event-launches 0 > $OUT/prof_$s.log 2>&1 || { echo "prof rc=$?"; exit 1; }
+  VMAS_FLOCK_SPLIT=$s timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/prof_$s -o run --output-format csv -- python bench.py --full --scenario flocking --cpu-steps 0 --steps 30 --event-launches 0 > $OUT/prof_$s.log 2>&1 || { echo "prof rc=$?"; exit 1; }
   f=$(find $OUT/prof_$s -name 'run_kernel_stats.csv' | head -1); echo "split=$s"; grep -E "k_flocking|k_world|k_copy_draw" "$f" | cut -d, -f1-4 | cut -c1-140
 done
 echo "session done"

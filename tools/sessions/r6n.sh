@@ -11,7 +11,7 @@ for m in 1 2; do
 done
 for i in 1 2 3; do
   for m in 0 1 2; do
-    VMAS_JIT_TAIL_STORE=$m timeout -k 10 200 python bench.py --cpu-steps 0 --steps 300 > $OUT/c2_${m}_$i.log 2>&1 || { echo "bench rc=$?"; exit 1; }
+    VMAS_JIT_TAIL_STORE=$m timeout -k 10 200 python bench.py --full --cpu-steps 0 --steps 300 > $OUT/c2_${m}_$i.log 2>&1 || { echo "bench rc=$?"; exit 1; }
     python - $OUT/c2_${m}_$i.log $m <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

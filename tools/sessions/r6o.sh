@@ -6,7 +6,7 @@ OUT=${OUT:-gpurun_out/r6o2}; mkdir -p $OUT
 export TMPDIR=/tmp
 for i in 1 2 3 4 5; do
   for m in 0 1; do
-    VMAS_JIT_TAIL_STORE=$m timeout -k 10 200 python bench.py --cpu-steps 0 --steps 500 > $OUT/c2_${m}_$i.log 2>&1 || { echo "bench rc=$?"; exit 1; }
+    VMAS_JIT_TAIL_STORE=$m timeout -k 10 200 python bench.py --full --cpu-steps 0 --steps 500 > $OUT/c2_${m}_$i.log 2>&1 || { echo "bench rc=$?"; exit 1; }
     python - $OUT/c2_${m}_$i.log $m <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
