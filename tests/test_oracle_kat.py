@@ -3,90 +3,30 @@
 The reference ships no numeric golden vectors, so the oracle (and, through it, the engine) is
 pinned by closed-form cases of every building block: soft contact force, free-body drag +
 integration, gravity, friction, closest points, ray casts, joint torque.  Each step case is
-checked on the oracle AND on the native engine, on three targets:
-  * ``cpu``: the library's host backend, one env;
-  * ``gpu-relaxed``: the gfx950 world kernel k_world in its default relaxed fp32 math (hardware
-    rcp / sqrt / exp / log / sin / cos -- the kernel bench.py times), the case replicated over
-    64 envs (one full wavefront; every env must give the closed-form answer);
-  * ``gpu-exact``: the same with VMAS_JIT_MATH=exact (IEEE div / sqrt, ocml transcendentals).
+checked on the oracle AND on the native engine, on the four targets of tests/_kat.py (``cpu``,
+``gpu-relaxed``, ``gpu-exact``: k_world; ``gpu-generic``: k_step), the GPU ones over 70 envs.
+
+The second half of the file pins every contact class (line-line, sphere-line, box-sphere,
+box-line, box-box, hollow boxes) with force AND torque magnitudes on rotated bodies, the joints,
+and the integrator's clamps, drags, frictions and gravities at the level of a step.  Expected
+values are float64 ``math`` from the geometry in each test; the tolerance is the one rule of
+tests/_kat.py (``tol``), and each case shows that a plausible misreading (a wrong inertia, a
+dropped LINE_MIN_DIST, drag in every substep...) would lie more than 50 tolerances away.  Only
+unambiguous geometry is used (a line end or a box vertex against the interior of a line or a
+face): ties between closest-point candidates are decided by candidate order, not by a closed form.
 """
 import math
-from dataclasses import dataclass
 
 import numpy as np
 import pytest
 import torch
 
 from oracle import vmas_oracle as O
-from vectorizedmultiagentsimulator_amd.simulator.core import Agent, Box, Landmark, Line, Sphere, World
+from vectorizedmultiagentsimulator_amd.simulator.core import Agent, Box, Landmark, Line, Sphere
+from vectorizedmultiagentsimulator_amd.simulator.joints import Joint
 
-K = 1e-3  # contact_margin
-
-
-@dataclass
-class Target:
-    device: str
-    batch: int
-    math: str | None
-
-
-TARGETS = [
-    pytest.param(("cpu", 1, None), id="cpu"),
-    pytest.param(("cuda", 64, "relaxed"), id="gpu-relaxed", marks=pytest.mark.gpu),
-    pytest.param(("cuda", 64, "exact"), id="gpu-exact", marks=pytest.mark.gpu),
-]
-
-
-@pytest.fixture(params=TARGETS)
-def tgt(request, monkeypatch):
-    dev, batch, mode = request.param
-    if dev == "cuda":
-        if not torch.cuda.is_available():
-            pytest.skip("no ROCm GPU visible")
-        monkeypatch.setenv("VMAS_JIT_MATH", mode)  # read when the world kernel is generated
-        dev = "cuda:0"
-    return Target(dev, batch, mode)
-
-
-def softplus_pen(x):
-    return K * (max(0.0, x / K) + math.log1p(math.exp(-abs(x / K))))
-
-
-def world_with(*entities, tgt=None, **kw):
-    tgt = tgt or Target("cpu", 1, None)
-    w = World(tgt.batch, tgt.device, **kw)
-    for e in entities:
-        (w.add_agent if isinstance(e, Agent) else w.add_landmark)(e)
-    w._kat_target = tgt
-    return w
-
-
-def set_state(e, pos, vel=(0.0, 0.0), rot=0.0, ang=0.0, tgt=None):
-    tgt = tgt or Target("cpu", 1, None)
-    rep = lambda v: torch.tensor([v] * tgt.batch, dtype=torch.float32, device=tgt.device)  # noqa: E731
-    e.state.pos = rep(pos)
-    e.state.vel = rep(vel)
-    e.state.rot = rep([rot])
-    e.state.ang_vel = rep([ang])
-
-
-def step_both(w):
-    """(oracle result, engine result) of one step from the current state (CPU tensors)."""
-    expected, _ = O.oracle_step(w)
-    w.step()
-    t = w._kat_target
-    if t.device != "cpu":
-        assert w.engine.kernel_name == "k_world", "GPU KATs run the world-specialised kernel"
-        assert ("VMAS_PHYS_RELAXED" in w.engine.jit_source()) == (t.math == "relaxed")
-    return expected, O.snapshot(w)
-
-
-def allclose(t, value, rel=0.0, abs_=0.0):
-    """Every env of a [B, k] result equals the closed-form value (pytest.approx semantics)."""
-    t = t.detach().cpu().reshape(t.shape[0], -1)
-    want = torch.tensor(value, dtype=torch.float64).reshape(1, -1)
-    err = (t.double() - want).abs()
-    return bool((err <= torch.maximum(rel * want.abs(), torch.tensor(abs_, dtype=torch.float64))).all())
+from _kat import (C, DT, LMD, allclose, distinguishes, expect, pen, set_state, softplus_pen, step_both, tgt, tol,  # noqa: F401
+                  world_with)
 
 
 def test_sphere_sphere_contact_force(tgt):
@@ -246,3 +186,323 @@ def test_distance_queries_analytic(tgt):
     assert not bool(w.is_overlapping(a, b).any())
     set_state(a, (0.3, 0.0), tgt=tgt)
     assert bool(w.is_overlapping(a, b).all()) and bool((w.get_distance(a, b) == -1).all())
+
+
+# ---- every contact class, with torque magnitudes and rotated bodies ----------------------------
+def test_line_line_contact_force_and_torque(tgt):
+    """The lower end of a fixed vertical line hangs delta above the interior of a free horizontal
+    line, 0.3 from its centre: F = c pen(LMD - delta) pushes A down, tau = r x F = -0.3 F."""
+    delta = 0.004
+    a = Landmark("a", shape=Line(1.0), movable=True, rotatable=True)
+    b = Landmark("b", shape=Line(0.4))
+    w = world_with(a, b, drag=0.0, tgt=tgt)
+    set_state(a, (0.0, 0.0), tgt=tgt)
+    set_state(b, (0.3, 0.2 + delta), rot=math.pi / 2, tgt=tgt)
+    f = C * pen(LMD - delta)
+    inertia = 1.0 * 1.0**2 / 12
+    vel = [0.0, -f * DT]
+    ang = -0.3 * f / inertia * DT
+    L = LMD  # dist_min (dist = delta is smaller)
+    tv, ta = tol(L, f * DT), tol(L, ang, inv_m=0.3 / inertia)
+    res = step_both(w)
+    expect(w, res, 0, "vel", vel, tv, "line-line")
+    expect(w, res, 0, "ang_vel", [ang], ta, "line-line")
+    expect(w, res, 0, "rot", [ang * DT], ta * DT, "line-line")
+    distinguishes([ang], [-0.3 * f / (1.0 * 1.0**2 / 2) * DT], ta)  # inertia m L^2 / 2
+    distinguishes(vel, [0.0, -C * pen(-delta) * DT], tv)  # LINE_MIN_DIST omitted
+    distinguishes([ang], [-ang], ta)  # lever-arm sign
+
+
+def test_sphere_line_torque_magnitude(tgt):
+    """A fixed sphere rests on a free horizontal line 0.4 from its centre, centre one radius
+    above it: dist_min - dist = LMD, F = c pen(LMD) down, tau = -0.4 F."""
+    line = Landmark("line", shape=Line(1.0), movable=True, rotatable=True)
+    s = Landmark("s", shape=Sphere(0.05))
+    w = world_with(line, s, drag=0.0, tgt=tgt)
+    set_state(line, (0.0, 0.0), tgt=tgt)
+    set_state(s, (0.4, 0.05), tgt=tgt)
+    f = C * pen(LMD)
+    inertia = 1.0 / 12
+    vel, ang = [0.0, -f * DT], -0.4 * f / inertia * DT
+    L = 0.05 + LMD  # dist_min (dist = r)
+    tv, ta = tol(L, f * DT), tol(L, ang, inv_m=0.4 / inertia)
+    res = step_both(w)
+    expect(w, res, 0, "vel", vel, tv, "sphere-line")
+    expect(w, res, 0, "ang_vel", [ang], ta, "sphere-line")
+    distinguishes([ang], [-0.4 * f / (1.0 / 2) * DT], ta)  # inertia m L^2 / 2
+    distinguishes(vel, [0.0, -C * pen(0.0) * DT], tv)  # LINE_MIN_DIST omitted
+
+
+def test_rotated_box_sphere_off_axis(tgt):
+    """A free solid box (1 x 0.5, mass 2) at (0.2, -0.1), rotated by pi/6, with a fixed sphere at
+    box-local (0.53, 0.1): the surface point is local (0.5, 0.1), the inner point local (0, 0.1),
+    so d = 0.5 and F = c pen(r + LMD + 0.5 - 0.53) along the box's -x axis; tau = +0.1 F."""
+    th = math.pi / 6
+    ct, st = math.cos(th), math.sin(th)
+    box = Landmark("box", shape=Box(length=1.0, width=0.5), movable=True, rotatable=True, mass=2.0)
+    s = Landmark("s", shape=Sphere(0.05))
+    w = world_with(box, s, drag=0.0, tgt=tgt)
+    set_state(box, (0.2, -0.1), rot=th, tgt=tgt)
+    set_state(s, (0.2 + 0.53 * ct - 0.1 * st, -0.1 + 0.53 * st + 0.1 * ct), tgt=tgt)
+    d_min = 0.05 + LMD + 0.5
+    f = C * pen(d_min - 0.53)
+    inertia = 2.0 * (1.0**2 + 0.5**2) / 12
+    vel = [-(f / 2) * DT * ct, -(f / 2) * DT * st]
+    ang = 0.1 * f / inertia * DT
+    L = d_min  # 0.557 (dist = 0.53)
+    tv, ta = tol(L, (f / 2) * DT, inv_m=1 / 2), tol(L, ang, inv_m=0.1 / inertia)
+    res = step_both(w)
+    expect(w, res, 0, "vel", vel, tv, "box-sphere rotated")
+    expect(w, res, 0, "ang_vel", [ang], ta, "box-sphere rotated")
+    distinguishes([ang], [0.1 * f / (2.0 * 1.0**2 / 12) * DT], ta)  # the line's inertia for a box
+    distinguishes(vel, [-(C * pen(d_min - LMD - 0.53) / 2) * DT * ct, 0.0], tv)  # LMD omitted
+    distinguishes(vel, [-(f / 2) * DT, 0.0], tv)  # force along the world's axis, not the box's
+
+
+def test_box_line_contact(tgt):
+    """The lower end of a free vertical line hangs delta above the interior of a fixed solid box's
+    top face: inner point (0.2, 0), d = 0.25, F = c pen(LMD + 0.25 - (0.25 + delta)) up the
+    line's own axis, so no torque."""
+    delta = 0.004
+    box = Landmark("box", shape=Box(length=1.0, width=0.5))
+    line = Landmark("line", shape=Line(0.4), movable=True, rotatable=True)
+    w = world_with(box, line, drag=0.0, tgt=tgt)
+    set_state(box, (0.0, 0.0), tgt=tgt)
+    set_state(line, (0.2, 0.25 + delta + 0.2), rot=math.pi / 2, tgt=tgt)
+    f = C * pen(LMD + 0.25 - (0.25 + delta))
+    vel = [0.0, f * DT]
+    L = LMD + 0.25  # dist_min (dist = 0.25 + delta is smaller)
+    tv = tol(L, f * DT)
+    res = step_both(w)
+    expect(w, res, 1, "vel", vel, tv, "box-line")
+    expect(w, res, 1, "ang_vel", [0.0], 1e-6, "box-line")  # (fp32 cos(pi/2) leaves 3e-8)
+    distinguishes(vel, [0.0, C * pen(-delta) * DT], tv)  # LINE_MIN_DIST omitted
+    distinguishes(vel, [0.0, C * pen(LMD - delta - 0.25) * DT], tv)  # d of the solid box omitted
+
+
+def test_box_box_vertex_to_face(tgt):
+    """A fixed 0.2 square rotated by pi/4 points a vertex at the interior of a free box's right
+    face, delta away and 0.15 above its axis: d_a = 0.5, d_b = 0.1 sqrt 2, dist_min - dist =
+    LMD - delta; F pushes A along -x, tau = r x F = +0.15 F."""
+    delta = 0.004
+    a = Landmark("a", shape=Box(length=1.0, width=0.5), movable=True, rotatable=True, mass=2.0)
+    b = Landmark("b", shape=Box(length=0.2, width=0.2))
+    w = world_with(a, b, drag=0.0, tgt=tgt)
+    set_state(a, (0.0, 0.0), tgt=tgt)
+    set_state(b, (0.5 + delta + 0.2 / math.sqrt(2), 0.15), rot=math.pi / 4, tgt=tgt)
+    f = C * pen(LMD - delta)
+    inertia = 2.0 * (1.0**2 + 0.5**2) / 12
+    vel, ang = [-(f / 2) * DT, 0.0], 0.15 * f / inertia * DT
+    L = 0.5 + 0.1 * math.sqrt(2) + LMD  # dist_min = d_a + d_b + LMD
+    tv, ta = tol(L, (f / 2) * DT, inv_m=1 / 2), tol(L, ang, inv_m=0.15 / inertia)
+    res = step_both(w)
+    expect(w, res, 0, "vel", vel, tv, "box-box")
+    expect(w, res, 0, "ang_vel", [ang], ta, "box-box")
+    distinguishes(vel, [-(C * pen(-delta) / 2) * DT, 0.0], tv)  # LINE_MIN_DIST omitted
+    distinguishes([ang], [0.15 * f / (2.0 * (1.0**2 + 0.5**2) / 2) * DT], ta)  # inertia m (L^2 + W^2) / 2
+    distinguishes([ang], [-ang], ta)  # lever-arm sign
+
+
+def test_hollow_box_contains_sphere(tgt):
+    """A sphere inside a fixed hollow box, one radius from its right wall: the wall is a line,
+    F = c pen(LMD) pushes the sphere inward (-x).  A solid box would push it out through the
+    wall with its centre as the inner point."""
+    box = Landmark("box", shape=Box(length=1.0, width=0.5, hollow=True))
+    s = Landmark("s", shape=Sphere(0.05), movable=True)
+    w = world_with(box, s, drag=0.0, tgt=tgt)
+    set_state(box, (0.0, 0.0), tgt=tgt)
+    set_state(s, (0.45, 0.0), tgt=tgt)
+    f = C * pen(LMD)
+    vel = [-f * DT, 0.0]
+    L = 0.05 + LMD  # dist_min (dist = r)
+    tv = tol(L, f * DT)
+    res = step_both(w)
+    expect(w, res, 1, "vel", vel, tv, "hollow box")
+    distinguishes(vel, [C * pen(0.05 + LMD + 0.5 - 0.45) * DT, 0.0], tv)  # treated as solid
+    distinguishes(vel, [-C * pen(0.0) * DT, 0.0], tv)  # LINE_MIN_DIST omitted
+
+
+# ---- joints -------------------------------------------------------------------------------------
+JOINT_FORCE = 200.0
+
+
+def test_joint_spring(tgt):
+    """A dist-0 joint between sphere centres is a one-sided spring F = -joint_force pen(x) (the
+    repulsive half vanishes for dist > 0); the pair's own collision is skipped.  Two substeps."""
+    a = Landmark("a", shape=Sphere(0.05), movable=True)
+    b = Landmark("b", shape=Sphere(0.05))
+    w = world_with(a, b, drag=0.0, substeps=2, joint_force=JOINT_FORCE, tgt=tgt)
+    w.add_joint(Joint(a, b, anchor_a=(0.0, 0.0), anchor_b=(0.0, 0.0), dist=0.0))
+    set_state(a, (0.02, 0.0), tgt=tgt)
+    set_state(b, (0.0, 0.0), tgt=tgt)
+    x, v = 0.02, 0.0
+    for _ in range(2):
+        v += -JOINT_FORCE * pen(x) * 0.05
+        x += v * 0.05
+    L = 0.02  # the first distance (dist_min = 0)
+    tv = tol(L, v, c=JOINT_FORCE)
+    res = step_both(w)
+    expect(w, res, 0, "vel", [v, 0.0], tv, "joint spring")
+    expect(w, res, 0, "pos", [x, 0.0], tv * DT, "joint spring")
+    distinguishes([v], [-JOINT_FORCE * pen(0.02) * DT], tv)  # one substep of dt
+    distinguishes([v], [v + C * pen(0.1 - 0.02) * 0.05 + C * pen(0.1 - 0.01) * 0.05], tv)  # collision kept
+
+
+def test_joint_anchor_torque(tgt):
+    """A pinned, rotatable 0.4 x 0.2 box is joined at its anchor (1, 0) -- 0.2 from the centre along
+    its axis -- to a fixed sphere at (0.2, 0.03): F pulls the anchor toward the sphere with
+    joint_force pen(dist), tau = r x F turns the box; omega and theta advance per substep."""
+    box = Landmark("box", shape=Box(length=0.4, width=0.2), rotatable=True)
+    s = Landmark("s", shape=Sphere(0.05))
+    w = world_with(box, s, drag=0.0, substeps=2, joint_force=JOINT_FORCE, tgt=tgt)
+    w.add_joint(Joint(box, s, anchor_a=(1.0, 0.0), anchor_b=(0.0, 0.0), dist=0.0))
+    set_state(box, (0.0, 0.0), tgt=tgt)
+    set_state(s, (0.2, 0.03), tgt=tgt)
+    inertia = 1.0 * (0.4**2 + 0.2**2) / 12
+
+    def run(arm):
+        th, om = 0.0, 0.0
+        for _ in range(2):
+            rx, ry = arm * math.cos(th), arm * math.sin(th)
+            dx, dy = 0.2 - rx, 0.03 - ry
+            dist = math.hypot(dx, dy)
+            mag = JOINT_FORCE * pen(dist)
+            fx, fy = mag * dx / dist, mag * dy / dist
+            om += (rx * fy - ry * fx) / inertia * 0.05
+            th += om * 0.05
+        return th, om
+
+    th, om = run(0.2)
+    L = 0.03  # the anchor's first distance from the sphere (dist_min = 0)
+    ta = tol(L, om, inv_m=0.2 / inertia, c=JOINT_FORCE)
+    res = step_both(w)
+    expect(w, res, 0, "ang_vel", [om], ta, "joint anchor")
+    expect(w, res, 0, "rot", [th], ta * DT, "joint anchor")
+    for r in res:  # pinned: the box does not translate
+        assert allclose(r[0]["pos"], [0.0, 0.0]) and allclose(r[0]["vel"], [0.0, 0.0])
+    distinguishes([om], [run(0.4)[1]], ta)  # anchor scaled by the length, not the half length
+    distinguishes([om], [0.2 * JOINT_FORCE * pen(0.03) / inertia * DT], ta)  # one substep of dt
+
+
+# ---- the integrator: clamps, drags, frictions, gravities -----------------------------------------
+def test_speed_and_semidim_clamps(tgt):
+    a = Landmark("a", shape=Sphere(0.05), movable=True, max_speed=0.5)
+    w = world_with(a, drag=0.0, x_semidim=1.0, y_semidim=1.0, tgt=tgt)
+    set_state(a, (0.98, 0.0), vel=(3.0, 4.0), tgt=tgt)
+    tv = tol(0.0, 0.5)
+    res = step_both(w)
+    expect(w, res, 0, "vel", [0.3, 0.4], tv, "clamps")  # (3, 4) scaled to norm 0.5
+    expect(w, res, 0, "pos", [1.0, 0.04], tv * DT, "clamps")  # 0.98 + 0.03 stops at the semidim
+    distinguishes([0.3, 0.4], [0.5, 0.5], tv)  # a per-component clamp
+    distinguishes([1.0, 0.04], [1.01, 0.04], tv * DT)  # no semidim
+
+
+@pytest.mark.parametrize("substeps", [1, 4])
+def test_rotation_entity_drag_v_range(tgt, substeps):
+    """The entity's own drag (0.5) replaces the world's (0.1), once per step, for vel and ang_vel;
+    v_range clamps each component; rot advances by the dragged ang_vel."""
+    a = Landmark("a", shape=Box(length=0.6, width=0.2), movable=True, rotatable=True, v_range=0.2, drag=0.5)
+    w = world_with(a, drag=0.1, substeps=substeps, tgt=tgt)
+    set_state(a, (0.0, 0.0), vel=(1.0, -0.1), rot=0.3, ang=2.0, tgt=tgt)
+    tv, ta = tol(0.0, 0.2), tol(0.0, 1.0)
+    res = step_both(w)
+    expect(w, res, 0, "vel", [0.2, -0.05], tv, f"drag/v_range x{substeps}")
+    expect(w, res, 0, "ang_vel", [1.0], ta, f"drag/v_range x{substeps}")
+    expect(w, res, 0, "rot", [0.4], ta * DT, f"drag/v_range x{substeps}")
+    expect(w, res, 0, "pos", [0.02, -0.005], tv * DT, f"drag/v_range x{substeps}")
+    distinguishes([0.2, -0.05, 1.0], [0.2, -0.09, 1.8], tv)  # the world's drag
+    if substeps > 1:  # drag in every substep
+        distinguishes([0.2, -0.05, 1.0], [0.5**substeps, -0.1 * 0.5**substeps, 2.0 * 0.5**substeps], ta)
+
+
+@pytest.mark.parametrize("level", ["entity", "world"])
+def test_angular_friction(tgt, level):
+    """Friction torque = -sign(w) min(mu I, |w| / dt I): a fast body loses mu dt, a slow one stops."""
+    kw = dict(angular_friction=2.0)
+    for ang, want in ((1.0, 0.8), (0.05, 0.0)):
+        a = Landmark("a", shape=Box(length=0.6, width=0.2), rotatable=True, **(kw if level == "entity" else {}))
+        w = world_with(a, drag=0.0, tgt=tgt, **(kw if level == "world" else {}))
+        set_state(a, (0.0, 0.0), ang=ang, tgt=tgt)
+        ta = tol(0.0, 1.0)
+        res = step_both(w)
+        expect(w, res, 0, "ang_vel", [want], ta if want else 1e-7, f"angular friction {level}")
+        expect(w, res, 0, "rot", [want * DT], (ta if want else 1e-7) * DT, f"angular friction {level}")
+    distinguishes([0.8], [1.0 - 2.0 * DT / ((0.6**2 + 0.2**2) / 12)], ta)  # torque not scaled by I
+
+
+def test_world_linear_friction(tgt):
+    """mu m per component against the motion (|v| / dt m is larger here): v -= mu dt v / |v|."""
+    a = Landmark("a", shape=Sphere(0.05), movable=True, mass=2.0)
+    w = world_with(a, drag=0.0, linear_friction=2.0, tgt=tgt)
+    set_state(a, (0.0, 0.0), vel=(0.6, 0.8), tgt=tgt)
+    tv = tol(0.0, 1.0)
+    res = step_both(w)
+    expect(w, res, 0, "vel", [0.48, 0.64], tv, "world linear friction")
+    distinguishes([0.48, 0.64], [0.6 - 0.06, 0.8 - 0.08], tv)  # force not scaled by the mass
+    distinguishes([0.48, 0.64], [0.6 - 0.2, 0.8 - 0.2], tv)  # mu per component, not along v
+
+
+def test_entity_gravity_per_env(tgt):
+    """A [B, 2] entity gravity, a different row in every env, adds to the world's gravity."""
+    a = Landmark("a", shape=Sphere(0.05), movable=True, mass=2.0)
+    w = world_with(a, drag=0.0, gravity=(0.0, -0.5), tgt=tgt)
+    rows = [[0.3 + 0.01 * b, -0.7 + 0.02 * b] for b in range(tgt.batch)]
+    a.gravity = torch.tensor(rows, dtype=torch.float32, device=tgt.device)
+    set_state(a, (0.0, 0.0), tgt=tgt)
+    vel = [[gx * DT, (gy - 0.5) * DT] for gx, gy in rows]
+    tv = tol(0.0, max(math.hypot(*v) for v in vel))
+    res = step_both(w)
+    expect(w, res, 0, "vel", vel, tv, "entity gravity [B,2]")
+    expect(w, res, 0, "pos", [[vx * DT, vy * DT] for vx, vy in vel], tv * DT, "entity gravity [B,2]")
+    distinguishes(vel[0], [0.3 * DT, -0.7 * DT], tv)  # the world's gravity dropped
+    distinguishes(vel[0], [0.3 * DT * 2.0, -1.2 * DT * 2.0], tv)  # a force m g not divided by m
+
+
+def test_entity_gravity_scalar(tgt):
+    """A scalar entity gravity broadcasts onto both components."""
+    a = Landmark("a", shape=Sphere(0.05), movable=True, mass=2.0, gravity=-0.4)
+    w = world_with(a, drag=0.0, tgt=tgt)
+    set_state(a, (0.0, 0.0), tgt=tgt)
+    tv = tol(0.0, 0.04 * math.sqrt(2))
+    res = step_both(w)
+    expect(w, res, 0, "vel", [-0.04, -0.04], tv, "entity gravity scalar")
+    distinguishes([-0.04, -0.04], [0.0, -0.04], tv)  # taken as a y acceleration
+
+
+def test_agent_torque_clamps(tgt):
+    ag = Agent("ag", shape=Box(length=0.6, width=0.2), max_t=0.5, t_range=0.3)
+    w = world_with(ag, drag=0.0, tgt=tgt)
+    set_state(ag, (0.0, 0.0), tgt=tgt)
+    ag.state.torque = torch.tensor([[2.0]] * tgt.batch, device=tgt.device)
+    inertia = 1.0 * (0.6**2 + 0.2**2) / 12
+    ang = 0.3 / inertia * DT  # clamp_with_norm -> 0.5, then clamp +-0.3
+    ta = tol(0.0, ang)
+    res = step_both(w)
+    expect(w, res, 0, "torque", [0.3], 4 * 2.0**-23 * 0.3, "torque clamps")
+    expect(w, res, 0, "ang_vel", [ang], ta, "torque clamps")
+    distinguishes([ang], [0.5 / inertia * DT], ta)  # t_range skipped
+
+
+def test_collision_filter_removes_pair(tgt):
+    b = Landmark("b", shape=Sphere(0.05))
+    a = Landmark("a", shape=Sphere(0.05), movable=True, collision_filter=lambda e: e is not b)
+    w = world_with(a, b, drag=0.0, tgt=tgt)
+    set_state(a, (0.09, 0.0), tgt=tgt)
+    set_state(b, (0.0, 0.0), tgt=tgt)
+    for res in step_both(w):
+        assert (res[0]["vel"] == 0.0).all()  # (unfiltered: c pen(0.01) dt = 0.1, the first KAT)
+
+
+def test_newtons_third_law(tgt):
+    """Two movable spheres (masses 1 and 4) overlapping by 0.01: equal and opposite impulses."""
+    a = Landmark("a", shape=Sphere(0.05), movable=True, mass=1.0)
+    b = Landmark("b", shape=Sphere(0.05), movable=True, mass=4.0)
+    w = world_with(a, b, drag=0.0, tgt=tgt)
+    set_state(a, (0.0, 0.0), tgt=tgt)
+    set_state(b, (0.09, 0.0), tgt=tgt)
+    f = C * pen(0.1 - 0.09)
+    L = 0.1  # dist_min (dist = 0.09)
+    res = step_both(w)
+    expect(w, res, 0, "vel", [-f * DT, 0.0], tol(L, f * DT), "third law")
+    expect(w, res, 1, "vel", [f / 4 * DT, 0.0], tol(L, f / 4 * DT, inv_m=1 / 4), "third law")
+    distinguishes([f / 4 * DT], [f * DT], tol(L, f / 4 * DT, inv_m=1 / 4))  # impulse not scaled by 1 / m
