@@ -25,8 +25,8 @@ from oracle import vmas_oracle as O
 from vectorizedmultiagentsimulator_amd.simulator.core import Agent, Box, Landmark, Line, Sphere
 from vectorizedmultiagentsimulator_amd.simulator.joints import Joint
 
-from _kat import (C, DT, LMD, allclose, distinguishes, expect, pen, set_state, softplus_pen, step_both, tgt, tol,  # noqa: F401
-                  world_with)
+from _kat import (C, DT, LMD, allclose, assert_kernel, distinguishes, expect, pen, set_state, softplus_pen,  # noqa: F401
+                  step_both, tgt, tol, world_with)
 
 
 def test_sphere_sphere_contact_force(tgt):
@@ -506,3 +506,27 @@ def test_newtons_third_law(tgt):
     expect(w, res, 0, "vel", [-f * DT, 0.0], tol(L, f * DT), "third law")
     expect(w, res, 1, "vel", [f / 4 * DT, 0.0], tol(L, f / 4 * DT, inv_m=1 / 4), "third law")
     distinguishes([f / 4 * DT], [f * DT], tol(L, f / 4 * DT, inv_m=1 / 4))  # impulse not scaled by 1 / m
+
+
+def test_friction_totals_of_a_motion_that_is_not_integrated(tgt):
+    """World.forces_dict / torques_dict carry the friction of a velocity the entity keeps: the
+    reference applies friction to every entity (core.py:1998, 2053-2101) and only the integration
+    asks movable / rotatable.  a turns but does not move (force = -mu m v / |v|: (-0.36, -0.48)),
+    b moves but does not turn (torque = -mu I: -0.2 I); found by tests/test_world_fuzz.py seeds 17
+    and 23 (k_world exported zeros: the mass / inertia of such an entity was not passed)."""
+    a = Landmark("a", shape=Box(length=0.6, width=0.2), rotatable=True, mass=2.0, linear_friction=0.3)
+    b = Landmark("b", shape=Box(length=0.6, width=0.2), movable=True, mass=3.0, angular_friction=0.2)
+    w = world_with(a, b, drag=0.0, tgt=tgt)
+    w.export_forces = True
+    set_state(a, (0.0, 0.0), vel=(0.3, 0.4), tgt=tgt)
+    set_state(b, (2.0, 0.0), ang=0.5, tgt=tgt)
+    inertia = 3.0 * (0.6**2 + 0.2**2) / 12
+    _, ow = O.oracle_step(w)
+    w.step()
+    assert_kernel(w)
+    for who, fd, td, ents in (("oracle", ow.forces_dict, ow.torques_dict, ow.ents),
+                              ("engine", w.forces_dict, w.torques_dict, w.entities)):
+        assert allclose(fd[ents[0]], [-0.36, -0.48], rel=4 * 2.0**-23), (who, fd[ents[0]][0])
+        assert allclose(td[ents[1]], [-0.2 * inertia], rel=4 * 2.0**-23), (who, td[ents[1]][0])
+        assert allclose(td[ents[0]], [0.0]) and allclose(fd[ents[1]], [0.0, 0.0]), who
+    # (a total not scaled by the mass / inertia would be (-0.18, -0.24) and -0.2)

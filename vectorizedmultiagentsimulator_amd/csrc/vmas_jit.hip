@@ -583,8 +583,10 @@ struct Gen {
     static std::vector<int> value_fields_all(const VmasEntityDesc& d) {
         std::vector<int> f;
         const bool mov = d.flags & VMAS_F_MOVABLE, rotb = d.flags & VMAS_F_ROTATABLE;
-        if (mov) f.push_back(kPrmMass);
-        if (rotb) f.push_back(kPrmInertia);
+        // (friction scales with the mass / inertia whether or not that motion is integrated: the
+        // exported totals of a rotatable-only entity carry its linear friction, core.py:2053-2101)
+        if (mov || (d.flags & VMAS_F_LIN_FRIC)) f.push_back(kPrmMass);
+        if (rotb || (d.flags & VMAS_F_ANG_FRIC)) f.push_back(kPrmInertia);
         if (mov || rotb) f.push_back(kPrmDrag);
         if (d.flags & VMAS_F_LIN_FRIC) f.push_back(kPrmLinFric);
         if (d.flags & VMAS_F_ANG_FRIC) f.push_back(kPrmAngFric);
