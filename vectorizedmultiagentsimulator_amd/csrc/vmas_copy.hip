@@ -24,13 +24,11 @@ constexpr int kCopyThreads = 256, kCopyUnroll = 4, kMaxCopyBlocks = 1024;
 struct CopyArgs {
     VmasCopySpan s[VMAS_COPY_MAX_SPANS];
     int n;
-    int nt;  // non-temporal stores (VMAS_COPY_NT=1, an A/B knob): the destinations are fresh tensors
 };
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 static_assert(sizeof(CopyArgs) <= 4096, "kernel argument block");
 
 // blk / nblk: this workgroup's index among the span's nblk workgroups (grid-stride over them)
-template <typename T, bool NT = false>
+template <typename T>
 __device__ __forceinline__ void copy_units(const T* __restrict__ src, T* __restrict__ dst, int64_t n, int blk, int nblk) {
     const int64_t step = (int64_t)nblk * kCopyThreads;
     int64_t i = (int64_t)blk * kCopyThreads + threadIdx.x;
@@ -39,15 +37,12 @@ __device__ __forceinline__ void copy_units(const T* __restrict__ src, T* __restr
 #pragma unroll
         for (int k = 0; k < kCopyUnroll; ++k) v[k] = src[i + k * step];  // independent loads in flight
 #pragma unroll
-        for (int k = 0; k < kCopyUnroll; ++k) {
-            if constexpr (NT) __builtin_nontemporal_store(v[k], dst + i + k * step);
-            else dst[i + k * step] = v[k];
-        }
+        for (int k = 0; k < kCopyUnroll; ++k) dst[i + k * step] = v[k];
     }
     for (; i < n; i += step) dst[i] = src[i];
 }
 
-__device__ __forceinline__ void copy_span(const VmasCopySpan& s, bool nt, int blk, int nblk) {
+__device__ __forceinline__ void copy_span(const VmasCopySpan& s, int blk, int nblk) {
     if (s.nbytes == VMAS_COPY_STORE64) {  // a store span: the 8-byte value src at dst
         if (blk == 0 && threadIdx.x == 0) *reinterpret_cast<uint64_t*>(s.dst) = (uint64_t)(uintptr_t)s.src;
         return;
@@ -60,10 +55,7 @@ __device__ __forceinline__ void copy_span(const VmasCopySpan& s, bool nt, int bl
         return;
     }
     const uintptr_t al = (uintptr_t)s.src | (uintptr_t)s.dst | (uintptr_t)s.nbytes;
-    if ((al & 15) == 0 && nt)
-        copy_units<u32x4, true>(reinterpret_cast<const u32x4*>(s.src), reinterpret_cast<u32x4*>(s.dst), s.nbytes / 16,
-                                blk, nblk);
-    else if ((al & 15) == 0)
+    if ((al & 15) == 0)
         copy_units(reinterpret_cast<const uint4*>(s.src), reinterpret_cast<uint4*>(s.dst), s.nbytes / 16, blk, nblk);
     else if ((al & 3) == 0)
         copy_units(reinterpret_cast<const uint32_t*>(s.src), reinterpret_cast<uint32_t*>(s.dst), s.nbytes / 4, blk, nblk);
@@ -72,15 +64,15 @@ __device__ __forceinline__ void copy_span(const VmasCopySpan& s, bool nt, int bl
 }
 
 __global__ void __launch_bounds__(kCopyThreads) k_copy_spans(CopyArgs a) {
-    copy_span(a.s[blockIdx.y], a.nt != 0, (int)blockIdx.x, (int)gridDim.x);
+    copy_span(a.s[blockIdx.y], (int)blockIdx.x, (int)gridDim.x);
 }
 
 // The post-replay copies and the next step's random-action draw in ONE launch (vmas_copy_spans_draw).
-// Packed grid (default): item y (span y < n_spans, else draw column y - n_spans) owns the 1-D
-// workgroups [first[y], first[y + 1]) -- a copy span as many as its bytes need (<= 1024), a column
-// exactly torch's gx_draw -- so no workgroup is launched only to leave (the 2-D grid of
-// max(copy, draw) x items launched ~10 000 of them per step for ~1 000 that work).  VMAS_COPY_PACKED=0:
-// the 2-D grid (blockIdx.y = item, blocks beyond the item's share leave; an A/B knob).
+// Packed grid: item y (span y < n_spans, else draw column y - n_spans) owns the 1-D workgroups
+// [first[y], first[y + 1]) -- a copy span as many as its bytes need (<= 1024), a column exactly
+// torch's gx_draw -- so no workgroup is launched only to leave (a 2-D grid of max(copy, draw) x
+// items launched ~10 000 of them per step for ~1 000 that work; measured, rejected and removed
+// with the non-temporal-store and units-per-thread variants, last held by commit 7ff9a7c).
 constexpr int kMergedSpans = 96, kMergedCols = 16;
 struct CopyDrawArgs {
     VmasCopySpan s[kMergedSpans];
@@ -89,30 +81,22 @@ struct CopyDrawArgs {
     long long numel, snap;
     const unsigned long long* off_dev;  // (non-null: the columns' offsets are relative to *off_dev)
     int n_spans, gx_draw, mode, n_items;
-    int first[kMergedSpans + kMergedCols + 1];  // packed grid: the items' first workgroups (n_items + 1)
-    int gx_copy, packed;
+    int first[kMergedSpans + kMergedCols + 1];  // the items' first workgroups (n_items + 1)
 };
 static_assert(sizeof(CopyDrawArgs) <= 4096, "kernel argument block");
 
 __global__ void __launch_bounds__(kCopyThreads) k_copy_draw(CopyDrawArgs a) {
-    int y, blk;
-    if (a.packed) {  // the item owning this workgroup: the last y with first[y] <= blockIdx.x
-        const int bx = (int)blockIdx.x;
-        int lo = 0, hi = a.n_items - 1;
-        while (lo < hi) {
-            const int mid = (lo + hi + 1) >> 1;
-            if (a.first[mid] <= bx) lo = mid;
-            else hi = mid - 1;
-        }
-        y = lo;
-        blk = bx - a.first[y];
-    } else {
-        y = (int)blockIdx.y;
-        blk = (int)blockIdx.x;
-        if (y < a.n_spans ? blk >= a.gx_copy : blk >= a.gx_draw) return;
+    // the item owning this workgroup: the last y with first[y] <= blockIdx.x
+    const int bx = (int)blockIdx.x;
+    int lo = 0, hi = a.n_items - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (a.first[mid] <= bx) lo = mid;
+        else hi = mid - 1;
     }
+    const int y = lo, blk = bx - a.first[y];
     if (y < a.n_spans) {
-        copy_span(a.s[y], false, blk, a.packed ? a.first[y + 1] - a.first[y] : a.gx_copy);
+        copy_span(a.s[y], blk, a.first[y + 1] - a.first[y]);
         return;
     }
     VmasUniformColumn col = a.c[y - a.n_spans];
@@ -146,11 +130,9 @@ static bool span_ok(const VmasCopySpan& s) {
 extern "C" int32_t vmas_copy_spans(int32_t device, const VmasCopySpan* spans, int32_t n, void* stream) {
     if (n < 0 || (n > 0 && !spans) || device < 0) return vmas_aux::fail(VMAS_E_INVALID, "vmas_copy_spans: bad arguments");
     VMAS_AUX_HIP(hipSetDevice(device));
-    static const int nt = getenv("VMAS_COPY_NT") && getenv("VMAS_COPY_NT")[0] == '1';
     for (int first = 0; first < n; first += VMAS_COPY_MAX_SPANS) {
         CopyArgs a{};
         a.n = 0;
-        a.nt = nt;
         int64_t most = 0;  // units of the largest span (16-byte units: sets the grid)
         for (int i = first; i < std::min(n, first + VMAS_COPY_MAX_SPANS); ++i) {
             const VmasCopySpan& s = spans[i];
@@ -188,14 +170,12 @@ extern "C" int32_t vmas_copy_spans_draw(int32_t device, const VmasCopySpan* span
     unsigned long long inc = 0;
     vmas_uniform::grid_for(numel, max_blocks[device], &gx_draw, &inc);
     CopyDrawArgs a{};
-    int64_t most = 0;
     int n = 0;
     for (int i = 0; i < n_spans; ++i) {
         const VmasCopySpan& sp = spans[i];
         if (!span_ok(sp)) return vmas_aux::fail(VMAS_E_INVALID, "vmas_copy_spans_draw: bad span %d", i);
         if (sp.nbytes == 0 || (sp.nbytes > 0 && sp.src == sp.dst)) continue;
         a.s[n++] = sp;
-        most = std::max<int64_t>(most, sp.nbytes > 0 ? (sp.nbytes + 15) / 16 : 1);
     }
     for (int i = 0; i < n_cols; ++i) {
         if (!cols[i].out) return vmas_aux::fail(VMAS_E_INVALID, "vmas_copy_spans_draw: null column %d", i);
@@ -209,15 +189,7 @@ extern "C" int32_t vmas_copy_spans_draw(int32_t device, const VmasCopySpan* span
     a.n_spans = n;
     a.gx_draw = gx_draw;
     a.mode = mode;
-    const int64_t per_block = (int64_t)kCopyThreads * kCopyUnroll;
-    const int gx_copy = (int)std::max<int64_t>(1, std::min<int64_t>(kMaxCopyBlocks, (most + per_block - 1) / per_block));
-    static const int packed = !(getenv("VMAS_COPY_PACKED") && getenv("VMAS_COPY_PACKED")[0] == '0');
-    // packed grid: 16-byte units per thread a span's share is sized for (VMAS_COPY_UNITS, an A/B
-    // knob: 1 = four times the workgroups, each thread one load in flight)
-    static const int units_per_thread = getenv("VMAS_COPY_UNITS") ? std::max(1, std::min(kCopyUnroll, atoi(getenv("VMAS_COPY_UNITS")))) : kCopyUnroll;
-    const int64_t per_share = (int64_t)kCopyThreads * units_per_thread;
-    a.gx_copy = gx_copy;
-    a.packed = packed;
+    const int64_t per_share = (int64_t)kCopyThreads * kCopyUnroll;
     a.n_items = n + n_cols;
     int total = 0;
     for (int y = 0; y < n + n_cols; ++y) {
@@ -236,17 +208,12 @@ extern "C" int32_t vmas_copy_spans_draw(int32_t device, const VmasCopySpan* span
         --trace;
         int64_t bytes = 0;
         for (int i = 0; i < n; ++i) bytes += a.s[i].nbytes > 0 ? a.s[i].nbytes : 0;
-        fprintf(stderr, "[vmas_copy_spans_draw] spans %d cols %d numel %lld bytes %lld grid %d x %d (copy %d draw %d) packed %d\n",
-                n, n_cols, (long long)numel, (long long)bytes, std::max(gx_copy, gx_draw), n + n_cols, gx_copy, gx_draw,
-                total);
+        fprintf(stderr, "[vmas_copy_spans_draw] spans %d cols %d numel %lld bytes %lld workgroups %d (%d per draw column)\n",
+                n, n_cols, (long long)numel, (long long)bytes, total, gx_draw);
         for (int i = 0; i < n; ++i)
             fprintf(stderr, "  span %d: %lld bytes%s\n", i, (long long)a.s[i].nbytes, a.s[i].src ? "" : " (increment)");
     }
-    if (packed)
-        hipLaunchKernelGGL(k_copy_draw, dim3((unsigned)total), dim3(kCopyThreads), 0, (hipStream_t)stream, a);
-    else
-        hipLaunchKernelGGL(k_copy_draw, dim3((unsigned)std::max(gx_copy, gx_draw), n + n_cols), dim3(kCopyThreads), 0,
-                           (hipStream_t)stream, a);
+    hipLaunchKernelGGL(k_copy_draw, dim3((unsigned)total), dim3(kCopyThreads), 0, (hipStream_t)stream, a);
     VMAS_AUX_HIP(hipGetLastError());
     *increment = inc * (unsigned long long)n_cols;
     return VMAS_OK;

@@ -149,7 +149,6 @@ constexpr int kLdsOnePerCu = 150 * 1024;  // big worlds: one workgroup per CU (1
 
 // pointer-table sources of the kernel argument block
 enum Src { S_POS, S_VEL, S_ROT, S_ANG, S_GRAV, S_FORCE, S_TORQUE, S_JFIX };
-constexpr unsigned kPrmMaskDefault = 0x7FFu;
 // value fields of VmasEntityDesc passed as kernel arguments (Gen::value_fields)
 enum Prm { kPrmMass, kPrmInertia, kPrmDrag, kPrmLinFric, kPrmAngFric, kPrmMaxSpeed, kPrmVRange, kPrmMaxF, kPrmFRange,
            kPrmMaxT, kPrmTRange };
@@ -193,17 +192,9 @@ struct Gen {
     // exceed one workgroup's LDS (hundreds of box pairs) still run the world-specialised step and
     // its persistent fixed point; the rows' traffic then goes through L1 / L2
     bool global_rows = false;
-    int nw = kNW;         // waves per 64-env group
-    // 64-env groups per claimed work item (VMAS_JIT_NG, A/B): ng > 1 runs ng groups in one
-    // workgroup of nw * ng waves in lockstep -- waves [k * nw, (k + 1) * nw) run group k's copy of
-    // the per-wave code on its own LDS rows, all sharing the workgroup's barriers -- so the groups a
-    // CU holds finish together instead of the second workgroup of a CU trailing the first
-    int ng = 1;
+    int nw = kNW;         // waves per workgroup (one workgroup = one 64-env group)
     int prof_block = -1;  // >= 0: stamp s_memtime at every phase boundary of this workgroup
     bool relaxed = false;  // relaxed fp32 math (VMAS_JIT_MATH=relaxed, worlds without joints; see compile())
-    int prio_mode = 1;     // VMAS_JIT_PRIO=0 turns off the wave issue priority falling with the substep
-    bool entity_preload = true;  // VMAS_JIT_PRELOAD=0 (A/B): contribution reads inside their branches
-    bool pair_preload = true;    // VMAS_JIT_PAIR_PRELOAD=0 (A/B): other waves' entity rows read at each use
     std::vector<char> dyn, in_pair, need_trig, need_rot, split;
     std::vector<int> owner;  // wave owning a dynamic entity / loading a static pair entity
     std::vector<std::vector<int>> wave_ents, wave_static;
@@ -213,12 +204,6 @@ struct Gen {
     int n_split = 0;
     // LDS rows (64 floats each)
     std::vector<int> r_p, r_rot, r_trig, r_res;
-    // balance's epilogue reads the group's state from the rows (epi_src): velocity rows of the
-    // dynamic entities, published after the last substep; Q (its scratch) then sits on the pair
-    // result rows, dead by then
-    std::vector<int> r_v, r_w;
-    int res_first = 0, res_end = 0;
-    bool epi_src = false;  // (VMAS_JIT_EPI_SRC=1, A/B: measured slower so far, profiles/r06/)
     int n_rows = 0;
     // argument block
     std::vector<std::pair<int, int>> ptr_src, str_src;  // (Src, index); strides: (Src*4 + k, index)
@@ -297,26 +282,21 @@ struct Gen {
         // it is priced at half a contact; a split pair's finish is placed by the LPT with the
         // other tasks (last in its wave), priced at 3.  Measured (profiles/r01/run27_schedule):
         // k_world balance 66.3 -> 64.4 us, transport 10.2 -> 9.9 us against SS 1.0 and the
-        // finish placed after all other tasks.  VMAS_JIT_COST_SS / VMAS_JIT_COST_FINISH /
-        // VMAS_JIT_COST_PART (a box-line part) / VMAS_JIT_FINISH_LPT=0 override (A/B).
-        float kCost[7] = {1.5f, 0.5f, 2.0f, 1.8f, 2.2f, 7.4f, 30.f};
-        float finish_cost = 3.0f;
+        // finish placed after all other tasks.  (The environment overrides of these costs and of
+        // the finish placement were removed; commit 7ff9a7c was the last to hold them.)
+        const float kCost[7] = {1.5f, 0.5f, 2.0f, 1.8f, 2.2f, 7.4f, 30.f};
+        const float finish_cost = 3.0f;
         // (measured and rejected, profiles/r02/run10_sched: a table rescaled to relaxed-math VALU
         // counts and SIMD-aware placement (waves w and w + 4 share a SIMD) -- balance C2 k_world
         // 40.8 -> 42.6-45.7 us: the two workgroups on a CU map waves to SIMDs with different
         // rotations, so per-SIMD sums even out, and the per-wave makespan is what binds)
-        if (const char* c = getenv("VMAS_JIT_COST_SS")) kCost[VMAS_PAIR_SS] = (float)atof(c);
-        if (const char* c = getenv("VMAS_JIT_COST_FINISH")) finish_cost = (float)atof(c);
-        float bl_part_cost = 1.8f, bb_part_cost = 3.8f;  // a split box-line / box-box pair's part
-        if (const char* c = getenv("VMAS_JIT_COST_PART")) bl_part_cost = (float)atof(c);
-        const char* fl_lpt = getenv("VMAS_JIT_FINISH_LPT");
-        const bool finish_in_lpt = !(fl_lpt && fl_lpt[0] == '0');
-        std::vector<Task> all, finishes;
+        const float bl_part_cost = 1.8f, bb_part_cost = 3.8f;  // a split box-line / box-box pair's part
+        std::vector<Task> all;
         for (int p = 0; p < P; ++p) {
             if (split[p]) {
                 for (int k = 0; k < parts(pd[p].cls); ++k)
                     all.push_back({p, k, pd[p].cls == VMAS_PAIR_BL ? bl_part_cost : bb_part_cost});
-                (finish_in_lpt ? all : finishes).push_back({p, kFinish, finish_cost});
+                all.push_back({p, kFinish, finish_cost});
             } else {
                 all.push_back({p, kWhole, kCost[pd[p].cls]});
             }
@@ -338,7 +318,6 @@ struct Gen {
                 const int rb = b.part >= 0 ? 0 : b.part == kFinish ? 2 : 1;
                 return ra != rb ? ra < rb : a.pair < b.pair;
             });
-        for (const Task& t : finishes) place(t);
         // entity phase: dynamic entities over the waves by contribution count (LPT)
         owner.assign(E, -1);
         wave_ents.assign(nw, {});
@@ -375,24 +354,14 @@ struct Gen {
             if (need_rot[e]) r_rot[e] = rows(1);
             if (need_trig[e]) r_trig[e] = rows(4);
         }
-        res_first = n_rows;
         for (int p = 0; p < P; ++p) r_res[p] = rows(split[p] ? 4 * parts(pd[p].cls) + 8 : res_rows(p));
-        res_end = n_rows;
-        r_v.assign(E, -1);
-        r_w.assign(E, -1);
-        if (use_src())
-            for (int e = 0; e < E; ++e)
-                if (dyn[e]) {
-                    r_v[e] = rows(2);
-                    r_w[e] = rows(1);
-                }
         // rows + FL + DONE + the pass's mask words + the fixed point's reduction words (in the
-        // row buffer when it is large enough)
-        const long red = (!global_rows && (long)std::max(n_rows, 1) * 64 * ng >= nfl + 2) ? 0 : nfl + 2;
-        const long lds = (global_rows ? 0L : (long)n_rows * 256 * ng) + (long)nfl * 4 + 4 * (n_split * ng + 1) +
-                         4L * (nfl / 2) + 4 * red + (has_epi() && !epi_q_in_rows() ? (long)kEpiQRows * 256 * ng : 0L) +
-                         (has_epi() && epi_lds ? (long)(cfg.epilogue == VMAS_EPILOGUE_BALANCE ? sizeof(VmasBalanceIO)
-                                                                                            : sizeof(VmasTransportIO)) : 0L);
+        // row buffer when it is large enough) + a scenario program's scratch and argument block
+        const long red = (!global_rows && (long)std::max(n_rows, 1) * 64 >= nfl + 2) ? 0 : nfl + 2;
+        const long lds = (global_rows ? 0L : (long)n_rows * 256) + (long)nfl * 4 + 4 * (n_split + 1) +
+                         4L * (nfl / 2) + 4 * red + (has_epi() && !epi_q_in_rows() ? (long)kEpiQRows * 256 : 0L) +
+                         (has_epi() ? (long)(cfg.epilogue == VMAS_EPILOGUE_BALANCE ? sizeof(VmasBalanceIO)
+                                                                                   : sizeof(VmasTransportIO)) : 0L);
         if (lds > lds_budget) {
             *why = "LDS budget exceeded (" + it(lds) + " B)";
             return false;
@@ -442,18 +411,13 @@ struct Gen {
     const char* epi_type() const { return cfg.epilogue == VMAS_EPILOGUE_BALANCE ? "VmasBalanceIO" : "VmasTransportIO"; }
     // the call running the program for group g (vmas_programs.hpp balance_group / transport_group)
     std::string epi_call(const std::string& io, const std::string& g, const std::string& wave, const std::string& lane,
-                         const std::string& q, const std::string& src = "") const {
+                         const std::string& q) const {
         if (cfg.epilogue == VMAS_EPILOGUE_BALANCE)
-            return "balance_group(" + io + ", " + g + ", " + wave + ", " + it(nw) + ", " + lane + ", " + q + src + ")";
+            return "balance_group(" + io + ", " + g + ", " + wave + ", " + it(nw) + ", " + lane + ", " + q + ")";
         return "transport_group(" + io + ", " + g + ", " + wave + ", " + it(nw) + ", " + lane + ")";
     }
-    bool epi_q_in_rows() const {
-        return !global_rows && (use_src() ? res_end - res_first >= kEpiQRows : n_rows >= kEpiQRows);
-    }
-    // the epilogue's state from the rows (balance only; not with rows in global memory)
-    bool use_src() const { return epi_src && cfg.epilogue == VMAS_EPILOGUE_BALANCE && !global_rows; }
-    // Q's first row in the row buffer (epi_q_in_rows)
-    long epi_q_row() const { return use_src() ? res_first : 0; }
+    // the program's scratch Q at the start of the row buffer (idle between groups) when it fits
+    bool epi_q_in_rows() const { return !global_rows && n_rows >= kEpiQRows; }
     // byte offset of Args.epi (after the fixed pointers: the value slots follow it)
     size_t epi_offset() const { return 8 * (std::max<size_t>(ptr_src.size(), 1) + n_out() + 7 + (global_rows ? 1 : 0)); }
     // byte offset of Args.wbd (after epi): the state write-back's backup delta (0: off; see wb_text)
@@ -473,9 +437,9 @@ struct Gen {
     // expressions for entity e as seen by wave w (registers when w owns it)
     static std::string row(int r, int k = 0) { return "L[" + it((long)(r + k) * 64) + " + lane]"; }
     bool mine(int e, int w) const { return dyn[e] && owner[e] == w; }
-    // Other waves' entities a wave's pair tasks read: with pair_preload, held in registers (q/u/o
-    // <e>) -- static ones loaded once per group, dynamic ones at the top of each pair phase, all
-    // reads in flight together -- instead of LDS reads at each use (inside the pairs' branches).
+    // Other waves' entities a wave's pair tasks read are held in registers (q/u/o<e>) -- static
+    // ones loaded once per group, dynamic ones at the top of each pair phase, all reads in flight
+    // together -- instead of LDS reads at each use (inside the pairs' branches).
     std::vector<char> pre_pos, pre_trig, pre_rot;  // of the wave being generated
     std::string pos(int e, int w) const {
         if (mine(e, w)) return "p" + it(e);
@@ -557,30 +521,21 @@ struct Gen {
     // VALUES (mass, inertia, drag, frictions, speed / force / torque limits) are zero here and
     // come from the kernel arguments (a.prm, prm_slots), so a world whose values change (a mass
     // re-rolled on every reset, ref scenarios/debug/het_mass.py:48-54) keeps its code object.
-    // Which values are kernel arguments: bit k = entity value field k (kPrm*), bit 11 = the
-    // world's gravity and semidims.  Default 0x7FF: every entity value an argument, the world's
-    // values folded -- as arguments they cost balance's k_world ~0.8 us (+2.4 %; a folded zero
-    // gravity component and semidim clamps simplify; interleaved A/B, profiles/r03/run8_prm_ab),
-    // and scenarios change world values far more rarely than entity masses (a change rebuilds).
-    // VMAS_JIT_PRM_MASK overrides (A/B).
-    unsigned prm_mask = kPrmMaskDefault;
+    // Every entity value is an argument; the world's gravity and semidims are folded into the code
+    // -- as arguments they cost balance's k_world ~0.8 us (+2.4 %; a folded zero gravity component
+    // and semidim clamps simplify; interleaved A/B, profiles/r03/run8_prm_ab), and scenarios change
+    // world values far more rarely than entity masses (a change rebuilds).  (The mask choosing
+    // per field was removed; commit 7ff9a7c was the last to hold it.)
     std::string desc(int e) const {
         const VmasEntityDesc& d = ed[e];
-        auto v = [&](int k) { return (prm_mask >> k) & 1u ? std::string("0.f") : fl(prm_value(d, k)); };
         std::string o = "{" + it(d.shape) + ", " + it(d.flags) + "u, " + it(d.agent_index) + ", " + it(d.out_lin) + ", " +
                         it(d.out_rot) + ", " + it(d.out_force) + ", " + it(d.out_torque) + ", " + fl(d.radius) + ", " +
                         fl(d.half_length) + ", " + fl(d.half_width);
-        for (int k = 0; k <= kPrmTRange; ++k) o += ", " + v(k);
+        for (int k = 0; k <= kPrmTRange; ++k) o += ", 0.f";
         return o + "}";
     }
     // the value fields a dynamic entity's code reads (by its flags), in VmasEntityDesc order
-    std::vector<int> value_fields(const VmasEntityDesc& d) const {
-        std::vector<int> f = value_fields_all(d), out;
-        for (int k : f)
-            if ((prm_mask >> k) & 1u) out.push_back(k);
-        return out;
-    }
-    static std::vector<int> value_fields_all(const VmasEntityDesc& d) {
+    static std::vector<int> value_fields(const VmasEntityDesc& d) {
         std::vector<int> f;
         const bool mov = d.flags & VMAS_F_MOVABLE, rotb = d.flags & VMAS_F_ROTATABLE;
         // (friction scales with the mass / inertia whether or not that motion is integrated: the
@@ -604,10 +559,10 @@ struct Gen {
         return n[k];
     }
     // kernel-argument value slots: (entity, field) pairs, then the world's gravity x / y and
-    // semidims (kPrmWorld + 0..3); laid out once in plan()
+    // semidims ((-1, 0..3): part of the argument block's layout, not read by the code, which has
+    // them folded in); laid out once in plan()
     std::vector<std::pair<int, int>> prm_src;
     std::vector<int> prm_of;  // first slot of entity e's fields (-1 if none)
-    int prm_world = -1;
     void plan_params() {
         prm_src.clear();
         prm_of.assign(E, -1);
@@ -616,7 +571,6 @@ struct Gen {
             prm_of[e] = (int)prm_src.size();
             for (int k : value_fields(ed[e])) prm_src.push_back({e, k});
         }
-        prm_world = (int)prm_src.size();
         for (int k = 0; k < 4; ++k) prm_src.push_back({-1, k});
     }
     // prologue: the value slots into LDS, constant indices only (a loop indexing a.prm
@@ -806,8 +760,7 @@ struct Gen {
     void wave_body(std::string& o, int w) {
         o += "template <> __device__ __forceinline__ bool run<" + it(w) +
              ">(const Args& a, float* L, uint32_t* FL, uint32_t* DONE, const uint32_t* MSK, int lane, int b, int bb, "
-             "bool valid, long long rbd, bool bk, bool wbk, bool spec, bool spec_ok, uint32_t* QL" +
-             std::string(use_src() ? ", const VmasBalanceIO* prog" : "") + ") {\n";
+             "bool valid, long long rbd, bool bk, bool wbk, bool spec, bool spec_ok, uint32_t* QL) {\n";
         // prologue: static pair entities (loaded once), dynamic entities into registers
         std::string bk_code;  // the state write-back's backup stores (wb_helpers)
         for (int e : wave_static[w]) {
@@ -854,27 +807,22 @@ struct Gen {
         // the speculative first claim (loop_text): its result, waited for only here -- after this
         // wave's state loads are in flight -- and handed to every wave by the barrier below
         if (w == 0) o += "    if (spec && threadIdx.x == 0) QL[65] = spec_ok ? 1u : 0u;\n";
-        // the epilogue's row table (src_fns), behind the same barrier, after wave 0's loads are in flight
-        if (w == 0 && use_src()) o += "    if (prog) src_rows(a, prog, lane);\n";
         o += "    " + stamp(w, pro);
         o += "    __syncthreads();\n";
         o += "    const bool own = !spec || QL[65] != 0u;  // (a lost speculative claim: compute, store nothing)\n";
         if (!bk_code.empty()) o += "    if (bk && valid && own) {\n" + bk_code + "    }\n";
         o += "    " + stamp(w, pro + " + 1");
         std::vector<char> rp, rt, rr;
-        if (pair_preload) {
-            task_reads(w, rp, rt, rr);
-            for (int e = 0; e < E; ++e)  // static entities: once per group
-                if (!dyn[e] && (rp[e] || rt[e] || rr[e])) o += preload(e, rp[e], rt[e], rr[e]).substr(4);
-        }
+        task_reads(w, rp, rt, rr);
+        for (int e = 0; e < E; ++e)  // static entities: once per group
+            if (!dyn[e] && (rp[e] || rt[e] || rr[e])) o += preload(e, rp[e], rt[e], rr[e]).substr(4);
         o += "    for (int s = 0; s < a.S; ++s) {\n";
         // Issue priority falling with the substep: of the two workgroups on a CU the one behind
         // gets the issue slots, so they finish together instead of the second running its last
         // substeps alone at half occupancy (balance 40.6-41.0 -> 39.7-40.0 us, flocking 38.2 ->
         // 37.1 us, interleaved; priority by wave load measured no gain: profiles/r02/run14_prio)
-        if (prio_mode == 1)
-            o += "        if (4 * s < a.S) __builtin_amdgcn_s_setprio(3); else if (2 * s < a.S) __builtin_amdgcn_s_setprio(2);"
-                 " else if (4 * s < 3 * a.S) __builtin_amdgcn_s_setprio(1); else __builtin_amdgcn_s_setprio(0);\n";
+        o += "        if (4 * s < a.S) __builtin_amdgcn_s_setprio(3); else if (2 * s < a.S) __builtin_amdgcn_s_setprio(2);"
+             " else if (4 * s < 3 * a.S) __builtin_amdgcn_s_setprio(1); else __builtin_amdgcn_s_setprio(0);\n";
         std::vector<char> word(W, 0);  // mask words this wave reads
         for (const Task& t : wave_tasks[w]) word[t.pair >> 5] = 1;
         for (int e : wave_ents[w])
@@ -885,13 +833,11 @@ struct Gen {
         for (const Task& t : wave_tasks[w]) fword[t.pair >> 5] = 1;
         for (int k = 0; k < W; ++k)
             if (fword[k]) o += "        uint32_t fr" + it(k) + " = 0u, fz" + it(k) + " = 0u;\n";
-        if (pair_preload) {
-            for (int e = 0; e < E; ++e)  // dynamic entities: at the top of each pair phase
-                if (dyn[e] && (rp[e] || rt[e] || rr[e])) o += preload(e, rp[e], rt[e], rr[e]);
-            pre_pos = rp;
-            pre_trig = rt;
-            pre_rot = rr;
-        }
+        for (int e = 0; e < E; ++e)  // dynamic entities: at the top of each pair phase
+            if (dyn[e] && (rp[e] || rt[e] || rr[e])) o += preload(e, rp[e], rt[e], rr[e]);
+        pre_pos = rp;
+        pre_trig = rt;
+        pre_rot = rr;
         for (const Task& t : wave_tasks[w]) task_code(o, t, w);
         pre_pos.clear();
         pre_trig.clear();
@@ -914,33 +860,21 @@ struct Gen {
             // every contribution row read up front (independent LDS reads in flight together),
             // then added in the reference's order where its pair is active (a select: the same
             // sums as the branch)
-            if (entity_preload) {
-                int k = 0;
-                for (const Item& x : items[e]) {
-                    const int r = res(x.pair);
-                    const std::string c = "c" + it(k++);
-                    if (mov) o += "            const float " + c + "x = " + row(r) + ", " + c + "y = " + row(r, 1) + ";\n";
-                    if (rotb && x.torque) o += "            const float " + c + "t = " + row(r, x.side ? 3 : 2) + ";\n";
+            int k = 0;
+            for (const Item& x : items[e]) {
+                const int r = res(x.pair);
+                const std::string c = "c" + it(k++);
+                if (mov) o += "            const float " + c + "x = " + row(r) + ", " + c + "y = " + row(r, 1) + ";\n";
+                if (rotb && x.torque) o += "            const float " + c + "t = " + row(r, x.side ? 3 : 2) + ";\n";
+            }
+            k = 0;
+            for (const Item& x : items[e]) {
+                const std::string c = "c" + it(k++), m = mbit(x.pair);
+                if (mov) {
+                    const std::string sx = x.side ? "-" + c + "x" : c + "x", sy = x.side ? "-" + c + "y" : c + "y";
+                    o += "            fx = " + m + " ? fx + " + sx + " : fx; fy = " + m + " ? fy + " + sy + " : fy;\n";
                 }
-                k = 0;
-                for (const Item& x : items[e]) {
-                    const std::string c = "c" + it(k++), m = mbit(x.pair);
-                    if (mov) {
-                        const std::string sx = x.side ? "-" + c + "x" : c + "x", sy = x.side ? "-" + c + "y" : c + "y";
-                        o += "            fx = " + m + " ? fx + " + sx + " : fx; fy = " + m + " ? fy + " + sy + " : fy;\n";
-                    }
-                    if (rotb && x.torque) o += "            tq = " + m + " ? tq + " + c + "t : tq;\n";
-                }
-            } else {
-                for (const Item& x : items[e]) {
-                    const int r = res(x.pair);
-                    std::string body;
-                    if (mov)
-                        body += x.side ? "fx = fx + -" + row(r) + "; fy = fy + -" + row(r, 1) + "; "
-                                       : "fx = fx + " + row(r) + "; fy = fy + " + row(r, 1) + "; ";
-                    if (rotb && x.torque) body += "tq = tq + " + row(r, x.side ? 3 : 2) + "; ";
-                    if (!body.empty()) o += "            if " + mbit(x.pair) + " { " + body + "}\n";
-                }
+                if (rotb && x.torque) o += "            tq = " + m + " ? tq + " + c + "t : tq;\n";
             }
             if (cfg.export_forces) o += "            lfx" + s + " = fx; lfy" + s + " = fy; ltq" + s + " = tq;\n";
             o += "            integrate(D" + s + ", s, a.sdt, fx, fy, tq, HAS_XS, XS, HAS_YS, YS, p" + s + ", v" + s +
@@ -954,15 +888,6 @@ struct Gen {
         o += "        __syncthreads();\n";
         o += "        " + stamp(w, "s * 4 + 3");
         o += "    }\n";
-        // the velocity rows balance's epilogue reads (use_src)
-        if (use_src()) {
-            std::string vr;
-            for (int e : wave_ents[w])
-                if (r_v[e] >= 0)
-                    vr += "        " + row(r_v[e]) + " = v" + it(e) + ".x; " + row(r_v[e], 1) + " = v" + it(e) + ".y; " +
-                          row(r_w[e]) + " = w" + it(e) + ";\n";
-            if (!vr.empty()) o += "    if (a.epi) {\n" + vr + "    }\n";
-        }
         // epilogue: the integrated fields into the fresh output tensors
         if (!wave_ents[w].empty()) {
             o += "    if (valid && own) {\n";
@@ -1026,130 +951,60 @@ struct Gen {
                "    float* q = const_cast<float*>(p);\n    q[(long)b * s0] = v.x;\n    q[(long)b * s0 + s1] = v.y;\n}\n\n";
     }
 
-    // Balance's epilogue reads the group's state from the rows (use_src): which row holds the
-    // tensor an argument-block pointer names -- a dynamic entity's output (the fresh output buffer,
-    // this launch's a.out) or a static entity's input (a.ptr) -- compared pointer and strides, once
-    // per workgroup by thread 0 (prologue); -1: not held in a row, the program reads the tensor.
-    std::string src_fns() const {
-        std::string rp = "__device__ __forceinline__ int row_pos(const Args& a, const float* p, int s0, int s1) {\n";
-        std::string rv = "__device__ __forceinline__ int row_vel(const Args& a, const float* p, int s0, int s1) {\n";
-        std::string rr = "__device__ __forceinline__ int row_rot(const Args& a, const float* p, int s0) {\n";
-        std::string rw = "__device__ __forceinline__ int row_ang(const Args& a, const float* p, int s0) {\n";
-        for (int e = 0; e < E; ++e) {
-            const VmasEntityDesc& d = ed[e];
-            if (r_p[e] >= 0) {
-                if (dyn[e] && d.out_lin >= 0)
-                    rp += "    if (p == a.out[0] + (size_t)" + it(d.out_lin) + " * a.B * 2 && s0 == 2 && s1 == 1) return " +
-                          it(r_p[e]) + ";\n";
-                else if (!dyn[e] || d.out_lin < 0)
-                    rp += "    if (p == " + P_(S_POS, e) + " && s0 == " + S_(S_POS, 0, e) + " && s1 == " + S_(S_POS, 1, e) +
-                          ") return " + it(r_p[e]) + ";\n";
-            }
-            if (r_rot[e] >= 0) {
-                if (dyn[e] && d.out_rot >= 0)
-                    rr += "    if (p == a.out[2] + (size_t)" + it(d.out_rot) + " * a.B && s0 == 1) return " + it(r_rot[e]) + ";\n";
-                else if (!dyn[e] || d.out_rot < 0)
-                    rr += "    if (p == " + P_(S_ROT, e) + " && s0 == " + S_(S_ROT, 0, e) + ") return " + it(r_rot[e]) + ";\n";
-            }
-            if (r_v[e] >= 0 && d.out_lin >= 0)
-                rv += "    if (p == a.out[1] + (size_t)" + it(d.out_lin) + " * a.B * 2 && s0 == 2 && s1 == 1) return " +
-                      it(r_v[e]) + ";\n";
-            if (r_w[e] >= 0 && d.out_rot >= 0)
-                rw += "    if (p == a.out[3] + (size_t)" + it(d.out_rot) + " * a.B && s0 == 1) return " + it(r_w[e]) + ";\n";
-        }
-        const std::string end = "    return -1;\n}\n";
-        return rp + end + rv + end + rr + "    (void)a; (void)p; (void)s0;\n" + end + rw + "    (void)a; (void)p; (void)s0;\n" + end +
-               "__shared__ int ESRC[kBalFields];\n"
-               "// (wave 0, a field per lane: thread 0 alone walking the fields held every workgroup ~3 us)\n"
-               "__device__ __forceinline__ void src_rows(const Args& a, const VmasBalanceIO* io, int lane) {\n"
-               "    for (int f = lane; f < kBalFields; f += 64) {\n"
-               "        const float* p = nullptr;\n"
-               "        int s0 = 0, s1 = 0, kind = 0;  // 0 position, 1 velocity, 2 rotation, 3 angular velocity\n"
-               "        if (f < kBalLineRot) {\n"
-               "            const VmasShapeRef* x = f == kBalPkgPos ? &io->package : f == kBalGoalPos ? &io->goal\n"
-               "                                   : f == kBalLinePos ? &io->line : &io->floor;\n"
-               "            p = x->pos; s0 = x->pos_s0; s1 = x->pos_s1;\n"
-               "        } else if (f <= kBalFloorRot) {\n"
-               "            const VmasShapeRef* x = f == kBalLineRot ? &io->line : &io->floor;\n"
-               "            p = x->rot; s0 = x->rot_s0; kind = 2;\n"
-               "        } else if (f < kBalAgPos) {\n"
-               "            const VmasVec* v = f == kBalPkgVel ? &io->package_vel : f == kBalLineVel ? &io->line_vel : &io->line_ang_vel;\n"
-               "            p = v->p; s0 = v->s0; s1 = v->s1; kind = f == kBalLineAng ? 3 : 1;\n"
-               "        } else {\n"
-               "            const int i = f < kBalAgVel ? f - kBalAgPos : f - kBalAgVel;\n"
-               "            if (i < io->n_agents) {\n"
-               "                const VmasVec* v = f < kBalAgVel ? &io->agent_pos[i] : &io->agent_vel[i];\n"
-               "                p = v->p; s0 = v->s0; s1 = v->s1; kind = f < kBalAgVel ? 0 : 1;\n"
-               "            }\n"
-               "        }\n"
-               "        ESRC[f] = !p ? -1 : kind == 0 ? row_pos(a, p, s0, s1) : kind == 1 ? row_vel(a, p, s0, s1)\n"
-               "                              : kind == 2 ? row_rot(a, p, s0) : row_ang(a, p, s0);\n"
-               "    }\n}\n\n";
-    }
-
-    // The group loop: one copy per wave (loop_per_wave, the default), each calling its own run<w>,
-    // or one loop around a switch over the waves (VMAS_JIT_LOOP_PER_WAVE=0).  With one loop the
-    // compiler hoists the loop-invariant address / stride values of EVERY wave's body above it,
-    // all live at once (balance: 106 SGPRs and 163 v_writelane spills of them into VGPR lanes,
-    // read back with v_readlane -- VALU instructions); with a loop per wave only that wave's are.
-    bool loop_per_wave = true;  // (required by ng > 1)
-    // the launch's first group run before its claim is confirmed (loop_text; VMAS_JIT_SPEC_CLAIM=0: claimed first)
-    bool spec_claim = true;
+    // The group loop: one copy per wave (group_loop<w>), each calling its own run<w>.  (One loop
+    // around a switch over the waves made the compiler hoist the loop-invariant address / stride
+    // values of EVERY wave's body above it, all live at once -- balance: 106 SGPRs and 163
+    // v_writelane spills; measured, rejected and removed, as were two 64-env groups per workgroup
+    // in lockstep, the first group claimed before it runs, and the program's argument block read
+    // through Args.epi instead of its LDS copy.  Commit 7ff9a7c was the last to hold them.)
     // Args.tail (vmas_tail.hpp): a replay's post-replay work run after the final decision, for the
     // modules whose k_world a kernel chain can fuse into one launch (a scenario program); dropped
     // when the argument block would outgrow kMaxArgBytes.  VMAS_JIT_TAIL=0: none (A/B).
     bool tail = false;
-    // the scenario program's argument block copied into LDS at the launch's start (epi_lds, the
-    // default; VMAS_JIT_EPI_LDS=0: read through Args.epi): the epilogue's field reads are LDS reads
-    // instead of a cold scalar-cache miss per group
-    bool epi_lds = true;
-    std::string epi_text(const std::string& io) const {
+    std::string epi_text() const {
         if (!has_epi()) return "";
         // The scenario program of this group (vmas_graph_chain_build fuses a replay's k_world and
         // k_program_jit into this launch): it reads the group's fields the waves just stored --
         // visible to the whole workgroup after the barrier (its workgroup-scope release / acquire;
         // agent-scope fences here write back L2 per group: 38 -> 159 us per launch) -- each pass of
         // the fixed point re-running it after its group, the final pass's writes last (as the
-        // state outputs).  Q: the row buffer, idle between groups.
-        const std::string lb = ng > 1 ? "Ls" : "L";
-        const std::string q = epi_q_in_rows() ? lb + (epi_q_row() ? " + " + it(epi_q_row() * 64) : std::string())
-                                               : (ng > 1 ? "EQ + sub * " + it((long)kEpiQRows * 64) : "EQ");
-        // (balance: the group's state from the rows -- use_src, BalRows)
-        const std::string src = use_src() ? ", &SRC" : "";
+        // state outputs).  Its argument block is the LDS copy made at the launch's start
+        // (PROG_IOP: LDS reads instead of a cold scalar-cache miss per group).  Q: the row buffer,
+        // idle between groups.
         return "        if (a.epi) {\n"
                "            __syncthreads();\n"
-               + std::string(use_src() ? "            const BalRows SRC{" + lb + ", ESRC, lane};\n" : "") +
-               "            " + (ng > 1 ? epi_call(io, "g * " + it(ng) + " + sub", "WAVE", "lane", q, src)
-                                        : epi_call(io, "g", "wave", "lane", q, src)) + ";\n"
+               "            " + epi_call("*PROG_IOP", "g", "wave", "lane", epi_q_in_rows() ? "L" : "EQ") + ";\n"
                "            __syncthreads();\n"
                "        }\n";
     }
-    std::string loop_text(const std::string& run, const std::string& cur, const std::string& io) const {
+    std::string loop_text() const {
         // The launch's first group is this workgroup's own (g = blockIdx.x), run speculatively: its
         // claim's compare-and-swap is issued here and its result read only after the group's state
         // loads (run<0>), so the claim's round trip overlaps them; a lost claim (another workgroup
         // stole the group before this one started) discards the group -- no store, no epilogue, no
         // completion.  The cursor already points past it (world_body).
         return "    bool spec = persistent && spec_first, spec_ok = true, own = true;\n"
-               "    if (spec && threadIdx.x == 0) spec_ok = grid_claim(claim, (int)blockIdx.x, (" + cur + ")->base);\n"
+               "    if (spec && threadIdx.x == 0) spec_ok = grid_claim(claim, (int)blockIdx.x, (CURP)->base);\n"
                "    for (;;) {\n"
-               "        const int g = spec ? (int)blockIdx.x : grid_next(persistent, a.ctl, claim, a.mask, MSK, nwords, ngrp, " + cur + ", QL);\n"
+               "        const int g = spec ? (int)blockIdx.x : grid_next(persistent, a.ctl, claim, a.mask, MSK, nwords, ngrp, CURP, QL);\n"
                "        if (g < 0) break;\n" + block_stamp(4, "__builtin_amdgcn_s_memrealtime()") +
                "        if (persistent) {\n"
                "            for (int i = threadIdx.x; i < nfl; i += blockDim.x) FL[i] = 0u;\n"
                "            __syncthreads();\n"
                "        }\n"
                "        {\n"
-               "            const int b = " + std::string(ng > 1 ? "(g * " + it(ng) + " + sub) * 64 + lane" : "g * 64 + lane") + ";\n"
+               "            const int b = g * 64 + lane;\n"
                "            const bool valid = b < a.B;\n"
                "            const int bb = valid ? b : (a.B - 1);\n"
                "            // the state write-back (Args.wbd, wb_text): this pass's inputs, its backup\n"
                "            const bool wbx = persistent && a.wbd != 0;\n"
-               "            const long long rbd = (wbx && (" + cur + ")->pass > 0) ? a.wbd : 0ll;\n"
-               "            const bool bk = wbx && (" + cur + ")->pass == 0;\n" + run + "        }\n"
+               "            const long long rbd = (wbx && (CURP)->pass > 0) ? a.wbd : 0ll;\n"
+               "            const bool bk = wbx && (CURP)->pass == 0;\n"
+               "            own = run<WAVE>(a, L, FL, DONE, MSK, lane, b, bb, valid, rbd, bk, wbx, spec, spec_ok, QL);\n"
+               "        }\n"
                "        spec = false;\n"
-               "        if (!own) continue;\n" + epi_text(io) +
-               "        if (persistent && grid_finish(g, FL, nfl, a.blk, a.mask, MSK, a.ctl, a.err, a.herr, nwords, ngrp, " + cur + ",\n"
+               "        if (!own) continue;\n" + epi_text() +
+               "        if (persistent && grid_finish(g, FL, nfl, a.blk, a.mask, MSK, a.ctl, a.err, a.herr, nwords, ngrp, CURP,\n"
                "                                      a.max_pass, RED, &QL[65], a.tm, t0s.rt, t0s.sc))\n"
                "            poison_outputs(a);\n" + block_stamp(5, "__builtin_amdgcn_s_memrealtime()") +
                "    }\n";
@@ -1159,10 +1014,6 @@ struct Gen {
         std::string& o = src;
         o += "// generated by vmas_jit.hip for one world\n";
         if (relaxed) o += std::string(kRelaxedTag) + "\n#define VMAS_PHYS_RELAXED 1\n";
-        // A/B knob: VMAS_JIT_TRIG=guard generates round 4's entity trig (a lane-divergent branch to
-        // the library sin / cos beyond 16 rad) instead of the branch-free reduction (vmas_physics.hpp)
-        if (relaxed && getenv("VMAS_JIT_TRIG") && std::string(getenv("VMAS_JIT_TRIG")) == "guard")
-            o += "#define VMAS_TRIG_GUARD 1\n";
         o += std::string(kFlagsTag) + codegen_flags(relaxed) + "\n";
         if (prof_block >= 0) o += "#define VMAS_JIT_PROFILE_SLOTS 1\n";
         if (const char* mp = getenv("VMAS_JIT_TEST_PASSES"))  // (test knob: vmas_jit_ops.hpp grid_decide)
@@ -1185,31 +1036,23 @@ struct Gen {
         o += wb_helpers();
         o += "constexpr WorldK WK{" + fl(cfg.contact_margin) + ", " + fl(cfg.collision_force) + ", " +
              fl(cfg.joint_force) + ", " + fl(cfg.torque_constraint_force) + "};\n";
-        // world gravity and semidims: whether they apply is structure, their values are arguments
-        const std::string pw = it(prm_world);
-        // (the values are copied from the kernel arguments into LDS in the prologue and read from
-        // there where used: held in SGPRs for the whole launch they raised balance's SGPR
+        // (the entity values are copied from the kernel arguments into LDS in the prologue and read
+        // from there where used: held in SGPRs for the whole launch they raised balance's SGPR
         // spills 193 -> 289 and the static VALU count by 11 %)
         o += "__shared__ float PRM[" + it(std::max<size_t>(prm_src.size(), 1)) + "];\n";
-        if ((prm_mask >> 11) & 1u) {
-            o += "#define GX PRM[" + pw + "]\n#define GY PRM[" + pw + " + 1]\n";
-            o += "#define XS PRM[" + pw + " + 2]\n#define YS PRM[" + pw + " + 3]\n";
-        } else {
-            o += "constexpr float GX = " + fl(cfg.gravity_x) + ", GY = " + fl(cfg.gravity_y) + ";\n";
-            o += "constexpr float XS = " + fl(cfg.x_semidim) + ", YS = " + fl(cfg.y_semidim) + ";\n";
-        }
+        // world gravity and semidims: folded into the code (desc)
+        o += "constexpr float GX = " + fl(cfg.gravity_x) + ", GY = " + fl(cfg.gravity_y) + ";\n";
+        o += "constexpr float XS = " + fl(cfg.x_semidim) + ", YS = " + fl(cfg.y_semidim) + ";\n";
         o += "constexpr bool HAS_G = " + bl(cfg.has_world_gravity) + ";\n";
         o += "constexpr bool HAS_XS = " + bl(cfg.has_x_semidim) + ", HAS_YS = " + bl(cfg.has_y_semidim) + ";\n";
         for (int e = 0; e < E; ++e)
             if (dyn[e]) o += "constexpr VmasEntityDesc D" + it(e) + "c" + desc(e) + ";\n";
         o += "\ntemplate <int WAVE>\n__device__ __forceinline__ bool run(const Args& a, float* L, uint32_t* FL, "
              "uint32_t* DONE, const uint32_t* MSK, int lane, int b, int bb, bool valid, long long rbd, bool bk, bool wbk, "
-             "bool spec, bool spec_ok, uint32_t* QL" + std::string(use_src() ? ", const VmasBalanceIO* prog" : "") +
-             ");\n\n";
-        if (use_src()) o += src_fns();
+             "bool spec, bool spec_ok, uint32_t* QL);\n\n";
         for (int w = 0; w < nw; ++w) wave_body(o, w);
         // waves per SIMD the register budget must allow: 2 workgroups per CU (4) or 1 (2)
-        const int waves_per_eu = (lds_budget <= kLdsTwoPerCu ? 2 : 1) * nw * ng / 4;
+        const int waves_per_eu = (lds_budget <= kLdsTwoPerCu ? 2 : 1) * nw / 4;
         // NaN over every output field of the step (one workgroup; only after a fixed point that
         // did not converge within max_pass passes): the bad step is visible in its own results
         {
@@ -1223,43 +1066,34 @@ struct Gen {
                          " * a.B; i += blockDim.x) a.out[" + it(k) + "][i] = nan;\n";
             o += "}\n\n";
         }
-        // wave w's group loop (loop_per_wave): its copy of the persistent loop around run<w>
-        if (loop_per_wave) {
-            o += "template <int WAVE>\n__device__ __forceinline__ void group_loop(const Args& a, float* L, uint32_t* FL, uint32_t* DONE, "
-                 "uint32_t* MSK, uint32_t* QL, uint32_t* RED, float* EQ, GridCursor* CURP, uint32_t* claim, TimerStart t0s, "
-                 "bool persistent, bool spec_first, int nfl, int nwords, int ngrp, int lane, int wave" +
-                 std::string(ng > 1 ? ", int sub" : "") +
-                 std::string(has_epi() ? std::string(", const ") + epi_type() + "* PROG_IOP" : std::string()) + ") {\n    (void)EQ;\n";
-            if (ng > 1)  // (this wave's group: its rows and split-pair counters)
-                o += "    float* const Ls = L + sub * " + it((long)std::max(n_rows, 1) * 64) + ";\n"
-                     "    uint32_t* const DONEs = DONE + sub * " + it(n_split) + ";\n    (void)Ls;\n";
-            o += loop_text(ng > 1 ? "            own = run<WAVE>(a, Ls, FL, DONEs, MSK, lane, b, bb, valid, rbd, bk, wbx, spec, spec_ok, QL" + std::string(use_src() ? ", a.epi ? PROG_IOP : nullptr" : "") + ");\n"
-                                  : "            own = run<WAVE>(a, L, FL, DONE, MSK, lane, b, bb, valid, rbd, bk, wbx, spec, spec_ok, QL" + std::string(use_src() ? ", a.epi ? PROG_IOP : nullptr" : "") + ");\n",
-                           "CURP", "*PROG_IOP");
-            o += "}\n\n";
-        }
+        // wave w's group loop: its copy of the persistent loop around run<w>
+        o += "template <int WAVE>\n__device__ __forceinline__ void group_loop(const Args& a, float* L, uint32_t* FL, uint32_t* DONE, "
+             "uint32_t* MSK, uint32_t* QL, uint32_t* RED, float* EQ, GridCursor* CURP, uint32_t* claim, TimerStart t0s, "
+             "bool persistent, bool spec_first, int nfl, int nwords, int ngrp, int lane, int wave" +
+             std::string(has_epi() ? std::string(", const ") + epi_type() + "* PROG_IOP" : std::string()) + ") {\n    (void)EQ;\n";
+        o += loop_text();
+        o += "}\n\n";
         o += "__device__ __forceinline__ void world_body(const Args& a) {\n";
         if (global_rows)  // (this workgroup's slab: the same [row][lane] layout as the LDS rows)
             o += "    float* L = a.rows + (size_t)blockIdx.x * " + it((long)std::max(n_rows, 1) * 64) + ";\n";
         else
-            o += "    __shared__ __attribute__((aligned(16))) float L[" + it(std::max(n_rows, 1) * 64 * ng) + "];\n";
+            o += "    __shared__ __attribute__((aligned(16))) float L[" + it(std::max(n_rows, 1) * 64) + "];\n";
         o += "    __shared__ uint32_t FL[" + it(nfl) + "];\n";
-        if (has_epi() && !epi_q_in_rows()) o += "    __shared__ float EQ[" + it((long)kEpiQRows * 64 * ng) + "];\n";
-        if (has_epi() && epi_lds) o += std::string("    __shared__ __attribute__((aligned(16))) ") + epi_type() + " PROG_IO;\n";
-        o += "    __shared__ uint32_t DONE[" + it(std::max(n_split * ng, 1)) + "];\n";
+        if (has_epi() && !epi_q_in_rows()) o += "    __shared__ float EQ[" + it((long)kEpiQRows * 64) + "];\n";
+        if (has_epi()) o += std::string("    __shared__ __attribute__((aligned(16))) ") + epi_type() + " PROG_IO;\n";
+        o += "    __shared__ uint32_t DONE[" + it(std::max(n_split, 1)) + "];\n";
         // LDS of the device-side fixed point: the row buffer when it is large enough (it is
         // idle between groups), else its own array; QL: steal list + broadcast word
         const int red_words = nfl + 2;
         o += "    __shared__ uint32_t MSK[" + it(std::max(nfl / 2, 1)) + "];\n";
         o += "    __shared__ uint32_t QL[66];\n";
-        if (!global_rows && (long)std::max(n_rows, 1) * 64 * ng >= red_words)
+        if (!global_rows && (long)std::max(n_rows, 1) * 64 >= red_words)
             o += "    uint32_t* RED = reinterpret_cast<uint32_t*>(L);\n";
         else
             o += "    __shared__ uint32_t RED[" + it(red_words) + "];\n";
         o += "    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;\n";
-        o += "    const int nfl = 2 * a.S * " + it(W) + ", nwords = a.S * " + it(W) + ", ngrp = " +
-             (ng > 1 ? "(a.B + " + it(64 * ng - 1) + ") / " + it(64 * ng) : std::string("(a.B + 63) >> 6")) + ";\n"
-             "    for (int i = threadIdx.x; i < " + it(n_split * ng) + "; i += blockDim.x) DONE[i] = 0u;\n";
+        o += "    const int nfl = 2 * a.S * " + it(W) + ", nwords = a.S * " + it(W) + ", ngrp = (a.B + 63) >> 6;\n"
+             "    for (int i = threadIdx.x; i < " + it(n_split) + "; i += blockDim.x) DONE[i] = 0u;\n";
         // Host-driven loop (a.ctl null): one pass per launch, each workgroup strides over the
         // 64-env groups and ORs their activity words into its own blk row (read by
         // k_jit_flags_reduce).  Persistent launch (a.ctl set): the broadphase fixed point on the
@@ -1272,13 +1106,12 @@ struct Gen {
              "    uint32_t* claim = a.mask + " + it(vmas::grid_claim_offset((long)cfg.max_substeps * W)) + ";\n"
              "    const TimerStart t0s = device_timer_start(persistent ? a.tm : nullptr, true);\n"
              "    __shared__ GridCursor CUR;\n"
-             "    const bool spec_first = " + std::string(spec_claim ? "persistent && (int)blockIdx.x < ngrp" : "false") +
-             ";  // (the speculative first group: loop_text)\n"
+             "    const bool spec_first = persistent && (int)blockIdx.x < ngrp;  // (the speculative first group: loop_text)\n"
              "    if (threadIdx.x == 0)\n"
              "        CUR = GridCursor{0, (int)blockIdx.x + (spec_first ? (int)gridDim.x : 0), 0, 0, 0, persistent ? ld64(&a.ctl[kGridEpoch]) : 0ull};\n"
              "    for (int i = threadIdx.x; i < nfl; i += blockDim.x) FL[i] = 0u;\n"
              "    for (int i = threadIdx.x; i < nwords; i += blockDim.x) MSK[i] = ~ld_agent(&a.mask[i]);\n" +
-             std::string(has_epi() && epi_lds ?
+             std::string(has_epi() ?  // (the program's argument block into LDS: epi_text)
                  "    if (a.epi)\n"
                  "        for (int i = threadIdx.x; i < (int)(sizeof(PROG_IO) / 8); i += blockDim.x)\n"
                  "            reinterpret_cast<unsigned long long*>(&PROG_IO)[i] = reinterpret_cast<const unsigned long long*>(a.epi)[i];\n"
@@ -1293,23 +1126,14 @@ struct Gen {
                               : "") +
              (prof_block >= 0 ? "    if (threadIdx.x == 0) vmas_prof_blk = a.prof + " + it((long)(cfg.max_substeps * 4 + 2) * kMaxNW) + ";\n" : "") +
              "";
-        // the group loop (loop_text): one copy per wave (loop_per_wave), or one around a switch
-        if (loop_per_wave) {
-            // (ng > 1: one call site per wave body, the group index a run-time value)
-            std::string sw = ng > 1 ? "    switch (wave % " + it(nw) + ") {\n" : "    switch (wave) {\n";
-            for (int w = 0; w < nw; ++w)
-                sw += "        case " + it(w) + ": group_loop<" + it(w) + ">(a, L, FL, DONE, MSK, QL, RED, " +
-                      std::string(has_epi() && !epi_q_in_rows() ? "EQ" : "nullptr") +
-                      ", &CUR, claim, t0s, persistent, spec_first, nfl, nwords, ngrp, lane, wave" +
-                      std::string(ng > 1 ? ", wave / " + it(nw) : "") +
-                      std::string(has_epi() ? (epi_lds ? ", &PROG_IO" : ", a.epi") : "") + "); break;\n";
-            o += sw + "        default: break;\n    }\n";
-        } else {
-            std::string sw = "            switch (wave) {\n";
-            for (int w = 0; w < nw; ++w)
-                sw += "                case " + it(w) + ": run<" + it(w) + ">(a, L, FL, DONE, MSK, lane, b, bb, valid, rbd, bk, wbx, spec, spec_ok, QL" + std::string(use_src() ? (epi_lds ? ", a.epi ? &PROG_IO : nullptr" : ", a.epi") : "") + "); break;\n";
-            o += loop_text(sw + "                default: break;\n            }\n", "&CUR", epi_lds ? "PROG_IO" : "*a.epi");
-        }
+        // the group loop (loop_text), one copy per wave
+        std::string sw = "    switch (wave) {\n";
+        for (int w = 0; w < nw; ++w)
+            sw += "        case " + it(w) + ": group_loop<" + it(w) + ">(a, L, FL, DONE, MSK, QL, RED, " +
+                  std::string(has_epi() && !epi_q_in_rows() ? "EQ" : "nullptr") +
+                  ", &CUR, claim, t0s, persistent, spec_first, nfl, nwords, ngrp, lane, wave" +
+                  std::string(has_epi() ? ", &PROG_IO" : "") + "); break;\n";
+        o += sw + "        default: break;\n    }\n";
         o += block_stamp(3, "__builtin_amdgcn_s_memrealtime()") +
              std::string(tail ? "    // the replay's post-replay work (vmas_tail.hpp): every group's final pass is decided\n"
                                 "    if (persistent && a.tail.n_items > 0) vmas_tail::run(a.tail);\n" : "") +
@@ -1320,7 +1144,7 @@ struct Gen {
              "        return;\n"
              "    }\n"
              "}\n\n";
-        const std::string bounds = "__launch_bounds__(" + it(nw * ng * 64) + ", " + it(waves_per_eu) + ")";
+        const std::string bounds = "__launch_bounds__(" + it(nw * 64) + ", " + it(waves_per_eu) + ")";
         o += "extern \"C\" __global__ void " + bounds + " k_world(Args a) {\n    world_body(a);\n}\n";
         if (has_epi())  // the eager step's launch of the same program (vmas_jit_program_outputs)
             o += "\nextern \"C\" __global__ void __launch_bounds__(" + it(nw * 64) + ") k_program_jit(" + epi_type() + " io_arg) {\n"
@@ -1329,17 +1153,6 @@ struct Gen {
                  "    " + epi_call("io", "blockIdx.x", "(int)(threadIdx.x >> 6)", "(int)(threadIdx.x & 63)", "Q") + ";\n}\n";
     }
 };
-
-// Code-generation A/B knobs (environment): VMAS_JIT_PRIO, VMAS_JIT_PRELOAD, VMAS_JIT_PAIR_PRELOAD,
-// VMAS_JIT_LOOP_PER_WAVE, VMAS_JIT_EPI_LDS.
-void codegen_knobs(Gen& g) {
-    if (const char* pr = getenv("VMAS_JIT_PRIO")) g.prio_mode = atoi(pr);
-    if (const char* pl = getenv("VMAS_JIT_PRELOAD")) g.entity_preload = atoi(pl) != 0;
-    if (const char* pp = getenv("VMAS_JIT_PAIR_PRELOAD")) g.pair_preload = atoi(pp) != 0;
-    if (const char* lw = getenv("VMAS_JIT_LOOP_PER_WAVE")) g.loop_per_wave = atoi(lw) != 0 || g.ng > 1;
-    if (const char* el = getenv("VMAS_JIT_EPI_LDS")) g.epi_lds = atoi(el) != 0;
-    if (const char* sc = getenv("VMAS_JIT_SPEC_CLAIM")) g.spec_claim = atoi(sc) != 0;
-}
 
 // Plan a world: box pairs split with two workgroups per CU, else unsplit, else unsplit with the
 // whole LDS (one workgroup per CU).  VMAS_JIT_SPLIT=0 disables splitting.
@@ -1354,24 +1167,15 @@ std::unique_ptr<Gen> make_plan(const VmasWorldConfig& cfg, const std::vector<Vma
         bool global_rows;
     } tries[] = {{true, kLdsTwoPerCu, false}, {false, kLdsTwoPerCu, false}, {false, kLdsOnePerCu, false},
                  {false, kLdsOnePerCu, true}};
-    // VMAS_JIT_NG=2 (A/B): two 64-env groups per workgroup in lockstep (Gen::ng), LDS rows of both,
-    // one workgroup per CU; not for worlds whose rows live in global memory
-    const char* ngs = getenv("VMAS_JIT_NG");
-    const int ng_want = ngs && atoi(ngs) == 2 ? 2 : 1;
-    for (int ng = ng_want; ng >= 1; --ng)  // (a world too big for two groups' rows plans with one)
     for (const auto& t : tries) {
         if (t.split && !allow_split) continue;
-        if (ng > 1 && t.global_rows) continue;
         std::unique_ptr<Gen> g(new Gen(cfg, ed, pd, jd));
-        g->ng = ng;
-        if (const char* es = getenv("VMAS_JIT_EPI_SRC")) g->epi_src = atoi(es) != 0;  // (read before plan: rows)
-        if (const char* pm = getenv("VMAS_JIT_PRM_MASK")) g->prm_mask = (unsigned)strtoul(pm, nullptr, 0) & 0xFFFu;
         if ((size_t)cfg.max_substeps * g->W > 1024) {
             *why = "too many substeps x pairs";
             return nullptr;
         }
         g->split_boxes = t.split;
-        g->lds_budget = ng > 1 ? kLdsOnePerCu : t.budget;  // (ng > 1: one workgroup per CU)
+        g->lds_budget = t.budget;
         g->global_rows = t.global_rows;
         // 16 waves per workgroup once there are enough pair tasks to spread (measured: flocking
         // 81 pairs 72 -> 59 us, discovery 19.2 -> 16.3 us; balance's 24 tasks 67.7 -> 69.7 us)
@@ -1381,7 +1185,6 @@ std::unique_ptr<Gen> make_plan(const VmasWorldConfig& cfg, const std::vector<Vma
         g->nw = n_tasks >= 32 ? 16 : kNW;
         if (const char* nws = getenv("VMAS_JIT_WAVES")) g->nw = atoi(nws) == 16 ? 16 : kNW;
         if (force_nw) g->nw = force_nw;
-        if (g->ng > 1) g->nw = kNW;  // (8 waves per group: 16 per workgroup)
         why->clear();
         if (g->plan(why)) return g;
     }
@@ -1549,10 +1352,8 @@ struct VmasJitWorld {
     std::vector<VmasJointDesc> jd;
     std::string src;
     std::vector<std::pair<int, int>> ptr_src, str_src, prm_src;
-    unsigned prm_mask = kPrmMaskDefault;  // value fields passed as arguments (the others are folded in)
     size_t arg_bytes = 0;
     int W = 1, nblk = 0, nw = kNW;
-    int ng = 1;  // 64-env groups per work item (k_world runs nw * ng waves per workgroup)
     hipModule_t mod = nullptr;
     hipFunction_t fn = nullptr;  // k_world
     hipFunction_t fn_prog = nullptr;  // k_program_jit (cfg.epilogue: the scenario program's own kernel)
@@ -1655,7 +1456,6 @@ int32_t vmas_jit_world_create(const VmasWorldConfig* cfg, const VmasEntityDesc* 
         }
         Gen& g = *gp;
         if (const char* pb = getenv("VMAS_JIT_PROFILE")) g.prof_block = std::max(0, atoi(pb));
-        codegen_knobs(g);
         g.relaxed = relaxed_math(W->cfg);
         g.generate();
         std::vector<char> code;
@@ -1671,19 +1471,17 @@ int32_t vmas_jit_world_create(const VmasWorldConfig* cfg, const VmasEntityDesc* 
             return cleanup(jfail(VMAS_E_HIP, "hipModuleGetFunction"));
         int scratch = 0;
         (void)hipFuncGetAttribute(&scratch, HIP_FUNC_ATTRIBUTE_LOCAL_SIZE_BYTES, W->fn);
-        if (scratch == 0 || g.nw == kNW || g.ng > 1) break;
+        if (scratch == 0 || g.nw == kNW) break;
     }
     Gen& g = *gp;
     W->src = g.src;
     W->ptr_src = g.ptr_src;
     W->str_src = g.str_src;
     W->prm_src = g.prm_src;
-    W->prm_mask = g.prm_mask;
     W->arg_bytes = g.arg_bytes();
     W->W = g.W;
     W->nw = g.nw;
-    W->ng = g.ng;
-    W->nblk = (cfg->batch + 64 * g.ng - 1) / (64 * g.ng);
+    W->nblk = (cfg->batch + 63) / 64;
     if (g.has_epi()) {
         if (hipModuleGetFunction(&W->fn_prog, W->mod, "k_program_jit") != hipSuccess)
             return cleanup(jfail(VMAS_E_HIP, "hipModuleGetFunction(k_program_jit)"));
@@ -1738,7 +1536,7 @@ int32_t vmas_jit_world_create(const VmasWorldConfig* cfg, const VmasEntityDesc* 
         const std::string mode = gm ? gm : "persistent";
         int per_cu = 0, cus = 0;
         if (mode != "host" &&
-            hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, W->fn, W->nw * W->ng * 64, 0) == hipSuccess &&
+            hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, W->fn, W->nw * 64, 0) == hipSuccess &&
             hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, cfg->device) == hipSuccess &&
             per_cu > 0 && cus > 0) {
             W->grid = std::min(W->nblk, per_cu * cus);
@@ -1786,7 +1584,6 @@ int32_t vmas_jit_compile_check(const VmasWorldConfig* cfg, const VmasEntityDesc*
     std::unique_ptr<Gen> gp = make_plan(*cfg, ed, pd, jd, &why);
     if (!gp) return jfail(VMAS_E_INVALID, "world not specialised: %s", why.c_str());
     Gen& g = *gp;
-    codegen_knobs(g);
     g.relaxed = relaxed_math(*cfg);
     g.generate();
     std::vector<char> code;
@@ -1935,7 +1732,7 @@ int32_t vmas_jit_world_step(VmasJitWorld* W, const VmasStepIO* io, void* stream_
     JHIP(hipStreamIsCapturing(stream, &cap));
     const bool capturing = cap == hipStreamCaptureStatusActive;
     auto launch_plain = [&](int blocks, hipFunction_t fn, bool timed) -> int32_t {
-        const uint32_t threads = (uint32_t)(W->nw * W->ng) * 64;
+        const uint32_t threads = (uint32_t)W->nw * 64;
         if (!W->timing || capturing || !timed) {  // (a captured launch is timed by the device timer)
             JHIP(hipModuleLaunchKernel(fn, blocks, 1, 1, threads, 1, 1, 0, stream, nullptr, extra));
             return VMAS_OK;
@@ -2051,14 +1848,10 @@ int32_t vmas_jit_world_set_params(VmasJitWorld* W, const VmasWorldConfig* cfg, c
             a.out_rot != b.out_rot || a.out_force != b.out_force || a.out_torque != b.out_torque ||
             a.radius != b.radius || a.half_length != b.half_length || a.half_width != b.half_width)
             return jfail(VMAS_E_INVALID, "set_params: entity %d differs in structure", e);
-        for (int k = 0; k <= kPrmTRange; ++k)  // (fields folded into the code: VMAS_JIT_PRM_MASK)
-            if (!((W->prm_mask >> k) & 1u) && prm_value(a, k) != prm_value(b, k))
-                return jfail(VMAS_E_INVALID, "set_params: entity %d field %d is folded into the code", e, k);
     }
-    if (!((W->prm_mask >> 11) & 1u))
-        for (int k = 0; k < 4; ++k)
-            if (prm_world_value(c, k) != prm_world_value(*cfg, k))
-                return jfail(VMAS_E_INVALID, "set_params: the world values are folded into the code");
+    for (int k = 0; k < 4; ++k)
+        if (prm_world_value(c, k) != prm_world_value(*cfg, k))
+            return jfail(VMAS_E_INVALID, "set_params: the world values are folded into the code");
     // pairs (classes, order, broadphase radii, d_min) and joints (anchors, dist, fixed rotation)
     // are folded into the code
     if (c.n_pairs && memcmp(pairs, W->pd.data(), sizeof(VmasPairDesc) * (size_t)c.n_pairs) != 0)

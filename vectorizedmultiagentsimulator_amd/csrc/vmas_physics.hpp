@@ -102,11 +102,8 @@ VHD Real tclamp(Real x, Real lo, Real hi) { return tmin(tmax(x, lo), hi); }
 // 4.4e-7 at 1e8 rad, 6.8e-6 at 1e9 rad (where the third part's truncation shows) --
 // tests/test_fused.py::test_relaxed_trig_large_rotation_gpu runs bodies turned by up to 1e6 rad.  (Round 4's lane-divergent branch to the library sin / cos beyond 16 rad
 // kept the library's Payne-Hanek code and its registers in every world's kernel: +10 VGPRs and
-// +12.5 % VALU instructions per balance launch)
-#ifdef VMAS_TRIG_GUARD
-VHD Real tsin(Real x) { return fabsf(x) < 16.f ? __sinf(x) : sinf(x); }
-VHD Real tcos(Real x) { return fabsf(x) < 16.f ? __cosf(x) : cosf(x); }
-#else
+// +12.5 % VALU instructions per balance launch; rejected and removed, commit 7ff9a7c
+// was the last to hold it.)
 VHD Real red2pi(Real x) {
     const Real k = rintf(x * 0x1.45f306p-3f);
     Real r = __builtin_fmaf(-k, 6.28125f, x);
@@ -115,7 +112,6 @@ VHD Real red2pi(Real x) {
 }
 VHD Real tsin(Real x) { return __sinf(red2pi(x)); }
 VHD Real tcos(Real x) { return __cosf(red2pi(x)); }
-#endif
 VHD Real tlog1p(Real y) {
     const Real u = 1.f + y;
     return u == 1.f ? y : __logf(u) * (y / (u - 1.f));

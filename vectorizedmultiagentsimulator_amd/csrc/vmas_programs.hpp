@@ -182,27 +182,15 @@ __device__ __forceinline__ float xdist_spheres(const VmasShapeRef& a, const Vmas
 constexpr int kBalQRows = 28;
 __device__ __forceinline__ float* bal_q(float* Q, int row) { return Q + row * 64; }
 
-// Where the program reads the step's state.  Every launch outside k_world: the argument block's
-// tensors.  As k_world's epilogue (vmas_jit.hip epi_text): the LDS rows k_world already holds the
-// group's integrated state in (positions, rotations, velocities; a row index per field, -1 = read
-// the tensor), found by comparing the argument block's pointers with k_world's own output / input
-// tensors -- the same fp32 values, without the round trip to HBM that re-reading the step's just
-// written (write-through) outputs costs.
+// The step's state the program reads, by field, from the argument block's tensors.  (As k_world's
+// epilogue it could also read the LDS rows k_world holds the group's state in: measured slower,
+// rejected and removed; commit 7ff9a7c was the last to hold that variant.)
 enum BalField {
     kBalPkgPos, kBalGoalPos, kBalLinePos, kBalFloorPos, kBalLineRot, kBalFloorRot, kBalPkgVel, kBalLineVel,
-    kBalLineAng, kBalAgPos, kBalAgVel = kBalAgPos + VMAS_SCN_MAX_AGENTS, kBalFields = kBalAgVel + VMAS_SCN_MAX_AGENTS
-};
-struct BalRows {
-    const float* L;  // the row buffer ([row][lane], 64 floats per row)
-    const int* row;  // kBalFields row indices
-    int lane;
+    kBalLineAng, kBalAgPos, kBalAgVel = kBalAgPos + VMAS_SCN_MAX_AGENTS
 };
 template <class IO>
-__device__ __forceinline__ V2 bal_v2(IO& io, const BalRows* s, int f, int b) {
-    if (s) {
-        const int r = __builtin_amdgcn_readfirstlane(s->row[f]);  // (one value for the workgroup)
-        if (r >= 0) return mk(s->L[r * 64 + s->lane], s->L[(r + 1) * 64 + s->lane]);
-    }
+__device__ __forceinline__ V2 bal_v2(IO& io, int f, int b) {
     switch (f) {
         case kBalPkgPos: { const VmasShapeRef x = io.package; return ref_pos(x, b); }
         case kBalGoalPos: { const VmasShapeRef x = io.goal; return ref_pos(x, b); }
@@ -216,11 +204,7 @@ __device__ __forceinline__ V2 bal_v2(IO& io, const BalRows* s, int f, int b) {
     }
 }
 template <class IO>
-__device__ __forceinline__ float bal_f1(IO& io, const BalRows* s, int f, int b) {
-    if (s) {
-        const int r = __builtin_amdgcn_readfirstlane(s->row[f]);
-        if (r >= 0) return s->L[r * 64 + s->lane];
-    }
+__device__ __forceinline__ float bal_f1(IO& io, int f, int b) {
     switch (f) {
         case kBalLineRot: { const VmasShapeRef x = io.line; return ref_rot(x, b); }
         case kBalFloorRot: { const VmasShapeRef x = io.floor; return ref_rot(x, b); }
@@ -230,20 +214,20 @@ __device__ __forceinline__ float bal_f1(IO& io, const BalRows* s, int f, int b) 
 
 // side `side` of both box queries, env bb
 template <class IO>
-__device__ __forceinline__ void bal_side(IO& io, int bb, int side, int lane, float* Q, const BalRows* src = nullptr) {
+__device__ __forceinline__ void bal_side(IO& io, int bb, int side, int lane, float* Q) {
     const VmasShapeRef fl = io.floor, ln = io.line;
-    const float rb = bal_f1(io, src, kBalLineRot, bb);
-    const V2 pf = bal_v2(io, src, kBalFloorPos, bb);
-    const Trig tf = xtrig(bal_f1(io, src, kBalFloorRot, bb));
+    const float rb = bal_f1(io, kBalLineRot, bb);
+    const V2 pf = bal_v2(io, kBalFloorPos, bb);
+    const Trig tf = xtrig(bal_f1(io, kBalFloorRot, bb));
     const Seg sd = box_side(pf, tf, fl.length * 0.5f, fl.width * 0.5f, side);
     Pts q;
-    xclosest_points_line_line(sd, Seg{bal_v2(io, src, kBalLinePos, bb), mk(cosf(rb), sinf(rb)), ln.length * 0.5f}, &q.p1,
+    xclosest_points_line_line(sd, Seg{bal_v2(io, kBalLinePos, bb), mk(cosf(rb), sinf(rb)), ln.length * 0.5f}, &q.p1,
                               &q.p2);
     bal_q(Q, 4 * side + 0)[lane] = q.p1.x;
     bal_q(Q, 4 * side + 1)[lane] = q.p1.y;
     bal_q(Q, 4 * side + 2)[lane] = q.p2.x;
     bal_q(Q, 4 * side + 3)[lane] = q.p2.y;
-    const V2 ps = bal_v2(io, src, kBalPkgPos, bb);  // closest_point_box (physics.py:262-294), this side's candidate
+    const V2 ps = bal_v2(io, kBalPkgPos, bb);  // closest_point_box (physics.py:262-294), this side's candidate
     const V2 p = closest_point_line(sd.p, sd.dir, sd.half, ps, true);
     bal_q(Q, 16 + 3 * side + 0)[lane] = p.x;
     bal_q(Q, 16 + 3 * side + 1)[lane] = p.y;
@@ -252,17 +236,13 @@ __device__ __forceinline__ void bal_side(IO& io, int bb, int side, int lane, flo
 
 // done = on_the_ground + is_overlapping(package, goal)
 template <class IO>
-__device__ __forceinline__ void bal_done(IO& io, int b, bool og, const OutDelta& od, const BalRows* src = nullptr) {
+__device__ __forceinline__ void bal_done(IO& io, int b, bool og, const OutDelta& od) {
     const VmasShapeRef pk = io.package, gl = io.goal;
     // xdist_spheres' arithmetic: (|pa - pb| - r_a) - r_b
-    const float d = (xnorm(bal_v2(io, src, kBalPkgPos, b) - bal_v2(io, src, kBalGoalPos, b)) - pk.radius) - gl.radius;
+    const float d = (xnorm(bal_v2(io, kBalPkgPos, b) - bal_v2(io, kBalGoalPos, b)) - pk.radius) - gl.radius;
     moved(io.done, od.done)[b] = (og || d < 0.f) ? 1 : 0;
 }
 
-// (an A/B knob of the package / floor preload: -DVMAS_BAL_PRELOAD_POS=0 through VMAS_JIT_CFLAGS)
-#ifndef VMAS_BAL_PRELOAD_POS
-#define VMAS_BAL_PRELOAD_POS 1
-#endif
 // wave 0's own inputs of the reward block, loaded before the barrier (their latency under the
 // four waves' box queries instead of after them): the previous shaping, the goal, package and
 // floor positions
@@ -271,9 +251,9 @@ struct BalPre {
     V2 goal, pkg, pf;
 };
 template <class IO>
-__device__ __forceinline__ BalPre bal_preload(IO& io, int bb, const BalRows* src = nullptr) {
-    return BalPre{io.global_shaping[(long)bb * io.gs_s0], bal_v2(io, src, kBalGoalPos, bb), bal_v2(io, src, kBalPkgPos, bb),
-                  bal_v2(io, src, kBalFloorPos, bb)};
+__device__ __forceinline__ BalPre bal_preload(IO& io, int bb) {
+    return BalPre{io.global_shaping[(long)bb * io.gs_s0], bal_v2(io, kBalGoalPos, bb), bal_v2(io, kBalPkgPos, bb),
+                  bal_v2(io, kBalFloorPos, bb)};
 }
 
 // The reward block of env b from the sides in Q: closest_line_box's and closest_point_box's
@@ -300,11 +280,7 @@ __device__ __forceinline__ void bal_reward(IO& io, int b, int lane, const OutDel
         }
     }
     const VmasShapeRef pk = io.package;
-#if VMAS_BAL_PRELOAD_POS
     const V2 pkg = pre.pkg, goal = pre.goal, pf = pre.pf;  // (b == bb: wave 0's valid lanes only)
-#else
-    const V2 pkg = ref_pos(pk, b), goal = pre.goal, pf = ref_pos(io.floor, b);
-#endif
     // compute_on_the_ground: is_overlapping(line, floor) + is_overlapping(package, floor)
     // (canonical (box, line) / (box, sphere) branches, core.py:1932-1968)
     const float dsc = xnorm(pkg - cp), dsb = xnorm(pkg - pf), dcb = xnorm(pf - cp);
@@ -329,13 +305,13 @@ __device__ __forceinline__ void bal_reward(IO& io, int b, int lane, const OutDel
 
 // agent i's 16-entry observation in env b
 template <class IO>
-__device__ __forceinline__ void bal_obs(IO& io, int b, int i, const OutDelta& od, const BalRows* src = nullptr) {
-    const V2 pkg = bal_v2(io, src, kBalPkgPos, b), goal = bal_v2(io, src, kBalGoalPos, b);
-    const V2 lpos = bal_v2(io, src, kBalLinePos, b), pv = bal_v2(io, src, kBalPkgVel, b), lv = bal_v2(io, src, kBalLineVel, b);
-    const float law = bal_f1(io, src, kBalLineAng, b);
-    const float lrot = torch_remainder(bal_f1(io, src, kBalLineRot, b), io.pi);
+__device__ __forceinline__ void bal_obs(IO& io, int b, int i, const OutDelta& od) {
+    const V2 pkg = bal_v2(io, kBalPkgPos, b), goal = bal_v2(io, kBalGoalPos, b);
+    const V2 lpos = bal_v2(io, kBalLinePos, b), pv = bal_v2(io, kBalPkgVel, b), lv = bal_v2(io, kBalLineVel, b);
+    const float law = bal_f1(io, kBalLineAng, b);
+    const float lrot = torch_remainder(bal_f1(io, kBalLineRot, b), io.pi);
     const V2 pg = pkg - goal;
-    const V2 p = bal_v2(io, src, kBalAgPos + i, b), v = bal_v2(io, src, kBalAgVel + i, b);
+    const V2 p = bal_v2(io, kBalAgPos + i, b), v = bal_v2(io, kBalAgVel + i, b);
     const V2 dp = p - pkg, dl = p - lpos;
     float4* dst = reinterpret_cast<float4*>(moved(io.obs[i], od.obs) + (long)b * 16);
     dst[0] = make_float4(p.x, p.y, v.x, v.y);
@@ -348,21 +324,20 @@ __device__ __forceinline__ void bal_obs(IO& io, int b, int i, const OutDelta& od
 // barrier inside): waves 0-3 the four box sides, waves 4.. the observations, then wave 0 the
 // reward block and done.  Q: kBalQRows x 64 floats of LDS.
 template <class IO>
-__device__ __forceinline__ void balance_group(IO& io, int g, int wave, int nwave, int lane, float* Q,
-                                              const BalRows* src = nullptr) {
+__device__ __forceinline__ void balance_group(IO& io, int g, int wave, int nwave, int lane, float* Q) {
     const int b = g * 64 + lane;
     const bool valid = b < io.batch;
     const int bb = valid ? b : io.batch - 1;
     const OutDelta od = load_out_delta(io);
     const bool rew = io.what & VMAS_SCN_REWARD;
-    const BalPre pre = rew && wave == 0 ? bal_preload(io, bb, src) : BalPre{0.f, mk(0.f, 0.f), mk(0.f, 0.f), mk(0.f, 0.f)};
-    if (rew && wave < 4) bal_side(io, bb, wave, lane, Q, src);
+    const BalPre pre = rew && wave == 0 ? bal_preload(io, bb) : BalPre{0.f, mk(0.f, 0.f), mk(0.f, 0.f), mk(0.f, 0.f)};
+    if (rew && wave < 4) bal_side(io, bb, wave, lane, Q);
     if ((io.what & VMAS_SCN_OBS) && wave >= 4 && valid)
-        for (int i = wave - 4; i < io.n_agents; i += nwave - 4) bal_obs(io, b, i, od, src);
+        for (int i = wave - 4; i < io.n_agents; i += nwave - 4) bal_obs(io, b, i, od);
     __syncthreads();
     if (wave != 0 || !valid) return;
     if (rew) bal_reward(io, b, lane, od, Q, pre);
-    else if (io.what & VMAS_SCN_DONE) bal_done(io, b, io.on_the_ground[b] != 0, od, src);
+    else if (io.what & VMAS_SCN_DONE) bal_done(io, b, io.on_the_ground[b] != 0, od);
 }
 
 // ---- transport (transport.py:130-190; restated in scenarios/transport.py) -------------------------

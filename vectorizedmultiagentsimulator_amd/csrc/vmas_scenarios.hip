@@ -875,9 +875,8 @@ int32_t vmas_flocking_outputs(int32_t device, const VmasFlockingIO* io, void* st
     if (io->fast_lidar && io->n_rays <= kFlockFastRays && io->n_ray_targets <= kFlockFastTargets) {
         const dim3 grid((io->batch + 63) / 64, (io->n_policy + 3) / 4);
         const hipStream_t st = (hipStream_t)stream;
-        // flocking's 12 rays with 1..8 targets: the unrolled instantiation (VMAS_FLOCK_UNROLL=0: runtime form)
-        static const bool unroll = !getenv("VMAS_FLOCK_UNROLL") || getenv("VMAS_FLOCK_UNROLL")[0] != '0';
-        const int nt = unroll && io->n_rays == 12 ? io->n_ray_targets : 0;
+        // flocking's 12 rays with 1..8 targets: the unrolled instantiation (other counts: runtime form)
+        const int nt = io->n_rays == 12 ? io->n_ray_targets : 0;
         switch (nt) {
 #define VMAS_FLOCK_CASE(k) \
     case k: hipLaunchKernelGGL((k_flocking_fast<12, k>), grid, dim3(256), 0, st, *io); break;
@@ -937,9 +936,8 @@ int32_t vmas_discovery_outputs(int32_t device, const VmasDiscoveryIO* io, void* 
     if (io->what & VMAS_SCN_OBS) {
         bool fast = io->fast_lidar && io->n_entities <= kDiscFastEntities;
         for (int s = 0; s < io->n_lidars; ++s) fast = fast && io->n_rays[s] <= kDiscFastRays;
-        // a wave per (64 envs, agent, LIDAR) with two LIDARs (VMAS_DISC_OBS_SPLIT=0: per agent, A/B)
-        static const bool split = !(getenv("VMAS_DISC_OBS_SPLIT") && getenv("VMAS_DISC_OBS_SPLIT")[0] == '0');
-        if (fast && split && io->n_lidars == 2)
+        // a wave per (64 envs, agent, LIDAR) with two LIDARs (other LIDAR counts: a wave per agent)
+        if (fast && io->n_lidars == 2)
             hipLaunchKernelGGL(k_discovery_obs_split<2>, dim3(gx, (io->n_agents + 1) / 2), dim3(256), 0,
                                (hipStream_t)stream, *io);
         else if (fast)
