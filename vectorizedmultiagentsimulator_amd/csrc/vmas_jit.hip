@@ -393,6 +393,8 @@ struct Gen {
             const char* tl = getenv("VMAS_JIT_TAIL");
             tail = has_epi() && !(tl && tl[0] == '0');
             if (tail && arg_bytes() > kMaxArgBytes) tail = false;
+            // the tail's items in LDS (tail_stage): only within the budget
+            tail_stage = tail && lds + (long)sizeof(VmasTail) <= lds_budget;
         }
         if (arg_bytes() > kMaxArgBytes) {
             *why = "kernel argument block too large (" + it(arg_bytes()) + " B)";
@@ -961,6 +963,10 @@ struct Gen {
     // modules whose k_world a kernel chain can fuse into one launch (a scenario program); dropped
     // when the argument block would outgrow kMaxArgBytes.  VMAS_JIT_TAIL=0: none (A/B).
     bool tail = false;
+    // The tail's items copied into LDS by the launch's prologue (TL): behind the decision every
+    // read of them is an LDS read, none a cold scalar read of ~1 KB of kernel arguments.  A world
+    // whose LDS budget has no room for the copy reads them from the kernel arguments.
+    bool tail_stage = false;
     std::string epi_text() const {
         if (!has_epi()) return "";
         // The scenario program of this group (vmas_graph_chain_build fuses a replay's k_world and
@@ -1082,6 +1088,8 @@ struct Gen {
         if (has_epi() && !epi_q_in_rows()) o += "    __shared__ float EQ[" + it((long)kEpiQRows * 64) + "];\n";
         if (has_epi()) o += std::string("    __shared__ __attribute__((aligned(16))) ") + epi_type() + " PROG_IO;\n";
         o += "    __shared__ uint32_t DONE[" + it(std::max(n_split, 1)) + "];\n";
+        if (tail_stage)
+            o += "    __shared__ __attribute__((aligned(16))) VmasTail TL;\n";
         // LDS of the device-side fixed point: the row buffer when it is large enough (it is
         // idle between groups), else its own array; QL: steal list + broadcast word
         const int red_words = nfl + 2;
@@ -1108,13 +1116,23 @@ struct Gen {
              "    __shared__ GridCursor CUR;\n"
              "    const bool spec_first = persistent && (int)blockIdx.x < ngrp;  // (the speculative first group: loop_text)\n"
              "    if (threadIdx.x == 0)\n"
-             "        CUR = GridCursor{0, (int)blockIdx.x + (spec_first ? (int)gridDim.x : 0), 0, 0, 0, persistent ? ld64(&a.ctl[kGridEpoch]) : 0ull};\n"
+             "        CUR = GridCursor{0, (int)blockIdx.x + (spec_first ? (int)gridDim.x : 0), 0, 0, 0, persistent ? ld64(&a.ctl[kGridEpoch]) : 0ull, 0};\n"
              "    for (int i = threadIdx.x; i < nfl; i += blockDim.x) FL[i] = 0u;\n"
              "    for (int i = threadIdx.x; i < nwords; i += blockDim.x) MSK[i] = ~ld_agent(&a.mask[i]);\n" +
              std::string(has_epi() ?  // (the program's argument block into LDS: epi_text)
                  "    if (a.epi)\n"
                  "        for (int i = threadIdx.x; i < (int)(sizeof(PROG_IO) / 8); i += blockDim.x)\n"
                  "            reinterpret_cast<unsigned long long*>(&PROG_IO)[i] = reinterpret_cast<const unsigned long long*>(a.epi)[i];\n"
+                 : "") +
+             // (the tail's items into LDS, read from the kernel-argument segment by every thread --
+             // indexing the by-value argument itself would keep a private copy of it)
+             std::string(tail_stage ?
+                 "    if (persistent && a.tail.n_items > 0) {\n"
+                 "        const unsigned long long* ka = reinterpret_cast<const unsigned long long*>(\n"
+                 "            (const char*)__builtin_amdgcn_kernarg_segment_ptr() + " + it((long)tail_offset()) + ");\n"
+                 "        for (int i = threadIdx.x; i < (int)(sizeof(VmasTail) / 8); i += blockDim.x)\n"
+                 "            reinterpret_cast<unsigned long long*>(&TL)[i] = ka[i];\n"
+                 "    }\n"
                  : "") +
              prm_copy() +
              "    __syncthreads();\n" +
@@ -1136,7 +1154,8 @@ struct Gen {
         o += sw + "        default: break;\n    }\n";
         o += block_stamp(3, "__builtin_amdgcn_s_memrealtime()") +
              std::string(tail ? "    // the replay's post-replay work (vmas_tail.hpp): every group's final pass is decided\n"
-                                "    if (persistent && a.tail.n_items > 0) vmas_tail::run(a.tail);\n" : "") +
+                                "    if (persistent && a.tail.n_items > 0) " +
+                                    std::string(tail_stage ? "vmas_tail::run(TL)" : "vmas_tail::run(a.tail)") + ";\n" : "") +
              "    if (!persistent) {\n"
              "        if (!a.blk) return;\n"
              "        __syncthreads();\n"

@@ -248,10 +248,11 @@ __device__ __forceinline__ void grid_time(unsigned long long* tm, TimerStart t0s
 
 // Per-workgroup cursor of the persistent launch (LDS; thread 0 writes it, behind barriers):
 // pass within the launch, next own group, steal list length / position, start counted,
-// E of the launch.
+// E of the launch; fin: this workgroup decided the step's final pass.
 struct GridCursor {
     int pass, own, nl, il, started;
     u64 base;
+    int fin;
 };
 
 // Test knob (VMAS_JIT_TEST_PASSES=<n>, compiled into the generated source): every step runs at least
@@ -343,6 +344,7 @@ __device__ inline bool grid_decide(const uint32_t* blk, uint32_t* nmask, const u
                 grid_started(ctl);
                 CUR->started = 1;
             }
+            CUR->fin = 1;  // (grid_next: nothing left to claim or wait for)
             if (tm) grid_time(tm, t0s);
         }
         __syncthreads();
@@ -386,6 +388,9 @@ __device__ __attribute__((noinline)) int grid_next(bool persistent, uint32_t* ct
                                                    uint32_t* MSK, int nwords, int ngrp, GridCursor* CUR, uint32_t* QL) {
     GridCursor c = *CUR;
     int g = -1;
+    // The decider of the step's final pass knows the decision (grid_decide): no steal scan and no
+    // wait -- two dependent round trips off the path from the decision to the end of the launch.
+    if (c.fin) return g;
     for (;;) {
         if (c.own < ngrp) {
             const int own = c.own;

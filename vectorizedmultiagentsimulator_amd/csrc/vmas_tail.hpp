@@ -16,6 +16,10 @@
 // when its source is written through (sc1: k_world's state outputs st_out*, the programs' carried
 // outputs) and the tail loads it with agent-scope loads (L2 bypassed); everything the tail
 // writes is read by later launches only (the kernel boundary orders it).
+//
+// The tail is latency at the very end of the launch, so what it reads behind the decision is kept
+// near: k_world's prologue copies the items below into LDS and run() is given that copy (vmas_jit.hip
+// tail_stage), and the final pass's decider goes straight to its units (vmas_jit_ops.hpp grid_next).
 #pragma once
 
 #ifndef __HIPCC_RTC__  // (hipRTC: vmas_physics.hpp provides the fixed-width types)
