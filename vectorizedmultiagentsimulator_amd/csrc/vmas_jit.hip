@@ -15,10 +15,12 @@
 //     no class switch); entity/pair/joint/world constants are constexpr, so flag tests fold;
 //   * a dynamic entity's state, velocity and agent force/torque live in its owner wave's
 //     registers for the whole launch; positions, rotations and trig rows are published to LDS;
-//   * box-line / box-box pairs are split into their per-side parts (4 / 8 tasks) on several
-//     waves; a finish task (last in its wave's list) waits for the parts on an LDS counter,
-//     replays the reference's first-strict-minimum selection and finishes the contact.  Every
-//     wave runs all its parts before any finish, so the waits cannot deadlock;
+//   * box-box pairs are split into their per-side parts (8 tasks) on several waves; a finish task
+//     (last in its wave's list) waits for the parts on an LDS counter, replays the reference's
+//     first-strict-minimum selection and finishes the contact.  Every wave runs all its parts
+//     before any finish, so the waits cannot deadlock.  A box-line pair is one task that scans
+//     only the box sides that can hold the closest point (Gen::side_prune; with
+//     VMAS_JIT_SIDE_PRUNE=0 it is split into 4 parts like a box-box pair);
 //   * tasks are placed by longest-processing-time with class costs measured with
 //     tools/jit_phase_profile.py (a contact pair costs several times an out-of-contact one; the
 //     costs are for the contact case);
@@ -187,6 +189,18 @@ struct Gen {
     const std::vector<VmasJointDesc>& jd;
     int E, P, A, J, W, nfl;
     bool split_boxes = true;
+    // Box-line pairs as ONE task that scans only the box sides that can hold the closest point
+    // (vmas_physics.hpp side_bounds / pair_bl_pruned: exact, bit-identical to the full scan) instead
+    // of four per-side parts plus a finish on five waves.  Typically one side survives, so the
+    // whole pair costs about one part plus the finish -- and the wave that runs it is known when
+    // the tasks are placed, whichever side survives.  Measured on balance C2 (profiles/r08/side_prune):
+    // k_world step 42.9-43.5 -> 40.6-41.3 us.  Pruning INSIDE the split (each part testing its own
+    // side first) lost: the surviving side's wave pays the bounds on top of its full test and is
+    // the pair phase's makespan.  VMAS_JIT_SIDE_PRUNE=0 restores the split and the full scans.
+    bool side_prune = true;
+    bool splits(int cls) const {
+        return split_boxes && (cls == VMAS_PAIR_BB || (cls == VMAS_PAIR_BL && !side_prune));
+    }
     long lds_budget = kLdsTwoPerCu;
     // rows in a global-memory slab (one per workgroup, a.rows) instead of LDS: worlds whose rows
     // exceed one workgroup's LDS (hundreds of box pairs) still run the world-specialised step and
@@ -262,7 +276,7 @@ struct Gen {
             if (need_trig[e]) need_rot[e] = 1;
         }
         for (int p = 0; p < P; ++p) {
-            split[p] = split_boxes && (pd[p].cls == VMAS_PAIR_BL || pd[p].cls == VMAS_PAIR_BB);
+            split[p] = splits(pd[p].cls);
             if (split[p]) split_idx[p] = n_split++;
         }
         items.assign(E, {});
@@ -619,7 +633,7 @@ struct Gen {
                 return "pair_bs(" + pos(a, w) + ", " + trig(a, w) + ", " + fl(da.half_length) + ", " +
                        fl(da.half_width) + ", " + ha + ", " + pos(b, w) + ", " + dm + ", WK)";
             case VMAS_PAIR_BL:
-                return "pair_bl(" + pos(a, w) + ", " + trig(a, w) + ", " + fl(da.half_length) + ", " +
+                return std::string(side_prune ? "pair_bl_pruned(" : "pair_bl(") + pos(a, w) + ", " + trig(a, w) + ", " + fl(da.half_length) + ", " +
                        fl(da.half_width) + ", " + ha + ", " + pos(b, w) + ", " + trig(b, w) + ", " +
                        fl(db.half_length) + ", " + dm + ", WK)";
             case VMAS_PAIR_BB:
@@ -1180,6 +1194,8 @@ std::unique_ptr<Gen> make_plan(const VmasWorldConfig& cfg, const std::vector<Vma
                                std::string* why, int force_nw = 0) {
     const char* sp = getenv("VMAS_JIT_SPLIT");
     const bool allow_split = !(sp && sp[0] == '0');
+    const char* spr = getenv("VMAS_JIT_SIDE_PRUNE");  // (0: box-line pairs split, full side scans)
+    const bool side_prune = !(spr && spr[0] == '0');
     const struct {
         bool split;
         long budget;
@@ -1194,13 +1210,14 @@ std::unique_ptr<Gen> make_plan(const VmasWorldConfig& cfg, const std::vector<Vma
             return nullptr;
         }
         g->split_boxes = t.split;
+        g->side_prune = side_prune;
         g->lds_budget = t.budget;
         g->global_rows = t.global_rows;
         // 16 waves per workgroup once there are enough pair tasks to spread (measured: flocking
         // 81 pairs 72 -> 59 us, discovery 19.2 -> 16.3 us; balance's 24 tasks 67.7 -> 69.7 us)
         int n_tasks = 0;
         for (const auto& q : pd)
-            n_tasks += (t.split && (q.cls == VMAS_PAIR_BL || q.cls == VMAS_PAIR_BB)) ? Gen::parts(q.cls) + 1 : 1;
+            n_tasks += g->splits(q.cls) ? Gen::parts(q.cls) + 1 : 1;
         g->nw = n_tasks >= 32 ? 16 : kNW;
         if (const char* nws = getenv("VMAS_JIT_WAVES")) g->nw = atoi(nws) == 16 ? 16 : kNW;
         if (force_nw) g->nw = force_nw;

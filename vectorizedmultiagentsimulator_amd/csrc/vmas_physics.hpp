@@ -141,6 +141,9 @@ VHD Trig make_trig_for(Real rot, bool box) {
 // backend (one environment at a time) it is the predicate itself.
 __device__ __forceinline__ bool vote_all(bool b) { return __all(b); }
 __host__ __forceinline__ bool vote_all(bool b) { return b; }
+// true iff the predicate holds in no active lane
+__device__ __forceinline__ bool vote_none(bool b) { return __ballot(b) == 0ull; }
+__host__ __forceinline__ bool vote_none(bool b) { return !b; }
 
 // TorchUtils.clamp_with_norm (utils.py:168-173)
 VHD V2 clamp_with_norm(V2 t, Real max_norm) {
@@ -443,6 +446,105 @@ VHD PairOut pair_bb(V2 pa, Trig ta, Real hla, Real hwa, bool hol_a, V2 pb, Trig 
     const Pts q = select_min(8, [&](int i) { return bb_part(pa, ta, hla, hwa, pb, tb, hlb, hwb, i); });
     return bb_finish(pa, hol_a, pb, hol_b, q, dmin, w);
 }
+
+#ifndef VMAS_PHYS_GRAD
+// ---------------------------------------------------------------------------------------------
+// Side pruning (the world-specialised kernels' box-line pairs only; k_step, the host backend and
+// the gradient path run the full scans above and stay the bit-for-bit reference).
+//
+// The box narrowphases select the first strict minimum of a distance over the box's four sides.
+// A side whose distance provably exceeds the distance of another side can be left out of the scan
+// without changing the selected side or any bit of its points.  In the box frame (local x along
+// rv = (c0, s0), y along rv2 = (c1, s1)) a target -- a point, or a segment given by its centre
+// and its half vector -- has
+//   * an upper bound UB on the selected distance: the smaller of its end points' exact
+//     distances to the box outline (inside: min(hl - |x|, hw - |y|), outside: hypot(ex, ey));
+//   * per side i a lower bound LB_i on that side's distance: the distance between the target's
+//     axis-aligned bounding intervals and the side's own (per-axis gap, then hypot).
+// Side i is pruned iff LB_i > UB + 2 m in every lane of the wave (vote_none; per env on the host),
+// compared as squares.  The side attaining the true minimum has LB <= UB, so it is never pruned,
+// and a pruned side's computed distance exceeds the selected one whatever its place in the order.
+// The margin m = 2^-11 x (the largest magnitude among the operands: half extents, local and world
+// coordinates) is three orders above the few-ulp error of the full tests and scales with them;
+// every min / max here is NaN propagating (tmin / tmax) and an infinite operand makes the
+// threshold infinite, so a non-finite operand prunes nothing.  rv and rv2 are
+// sin / cos of rot and of fl(rot + pi/2): for a large |rot| the rounding of that sum skews the
+// frame, so nothing is pruned once |rv . rv2| exceeds 2^-14.
+struct SideBounds {
+    float t2;      // (UB + 2 m)^2
+    float lb2[4];  // LB_i^2, sides numbered as in box_side
+    bool ok;       // frame orthogonal enough for the bounds to hold
+};
+// squared distance of a point to the box outline, branch-free: outside ex^2 + ey^2 (then the last
+// term is 0), inside min(hl - |x|, hw - |y|)^2 (then ex = ey = 0); tmin / tmax carry a NaN through
+VHD float point_box_ub2(float x, float y, float hl, float hw) {
+    const float ox = fabsf(x) - hl, oy = fabsf(y) - hw;  // > 0: outside along that axis
+    const float ex = tmax(ox, 0.f), ey = tmax(oy, 0.f), in = tmin(tmax(ox, oy), 0.f);
+    return (ex * ex + ey * ey) + in * in;
+}
+VHD float gap3(float a, float b) { return tmax(tmax(a, b), 0.f); }
+// c: the target's centre, h: its half vector (zero for a point), both in world coordinates
+VHD SideBounds side_bounds(V2 pos, Trig t, float hl, float hw, V2 c, V2 h) {
+    const V2 d = c - pos;
+    const float cx = d.x * t.c0 + d.y * t.s0, cy = d.x * t.c1 + d.y * t.s1;
+    const float hx = h.x * t.c0 + h.y * t.s0, hy = h.x * t.c1 + h.y * t.s1;
+    const float ub = sqrtf(tmin(point_box_ub2(cx + hx, cy + hy, hl, hw), point_box_ub2(cx - hx, cy - hy, hl, hw)));
+    const float ax = fabsf(hx), ay = fabsf(hy);
+    const float scale = tmax(tmax(tmax(fabsf(cx), fabsf(cy)), tmax(ax, ay)),
+                             tmax(tmax(tmax(fabsf(pos.x), fabsf(pos.y)), tmax(fabsf(c.x), fabsf(c.y))), tmax(hl, hw)));
+    const float th = ub + scale * 0x1p-10f;  // UB + 2 m
+    const float xlo = cx - ax, xhi = cx + ax, ylo = cy - ay, yhi = cy + ay;
+    const float gxb = gap3(xlo - hl, -hl - xhi), gyb = gap3(ylo - hw, -hw - yhi);
+    const float gx0 = gap3(xlo - hl, hl - xhi), gx1 = gap3(xlo + hl, -hl - xhi);
+    const float gy2 = gap3(ylo - hw, hw - yhi), gy3 = gap3(ylo + hw, -hw - yhi);
+    SideBounds s;
+    s.t2 = th * th;
+    s.lb2[0] = gx0 * gx0 + gyb * gyb;
+    s.lb2[1] = gx1 * gx1 + gyb * gyb;
+    s.lb2[2] = gxb * gxb + gy2 * gy2;
+    s.lb2[3] = gxb * gxb + gy3 * gy3;
+    s.ok = fabsf(t.c0 * t.c1 + t.s0 * t.s1) <= 0x1p-14f;
+    return s;
+}
+VHD bool side_pruned(const SideBounds& s, int i) { return vote_none(!(s.ok && s.lb2[i] > s.t2)); }
+// bit i set: side i of the box cannot hold the closest point (wave-uniform on gfx950)
+VHD uint32_t side_prune_mask(V2 pos, Trig t, float hl, float hw, V2 c, V2 h) {
+    const SideBounds s = side_bounds(pos, t, hl, hw, c, h);
+    uint32_t m = 0u;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+        if (side_pruned(s, i)) m |= 1u << i;
+    return m;
+}
+VHD uint32_t line_prune_mask(V2 pos, Trig t, float hl, float hw, Seg line) {
+    return side_prune_mask(pos, t, hl, hw, line.p, mk(line.half * line.dir.x, line.half * line.dir.y));
+}
+
+// select_min over the parts whose bit in `pruned` is clear
+template <class PartFn>
+VHD Pts select_min_unpruned(int n, uint32_t pruned, PartFn part) {
+    Pts best{mk(INFINITY, INFINITY), mk(INFINITY, INFINITY)};
+    float bd = INFINITY;
+#pragma unroll 1
+    for (int i = 0; i < n; ++i) {
+        if ((pruned >> i) & 1u) continue;
+        const Pts q = part(i);
+        const float d = norm(q.p1 - q.p2);
+        if (d < bd) {
+            bd = d;
+            best = q;
+        }
+    }
+    return best;
+}
+// pair_bl over the unpruned sides of the box
+VHD PairOut pair_bl_pruned(V2 pbx, Trig tbx, float hl, float hw, bool hollow, V2 pl, Trig tl, float hll,
+                           float dmin, const WorldK& w) {
+    const uint32_t pm = line_prune_mask(pbx, tbx, hl, hw, Seg{pl, mk(tl.c0, tl.s0), hll});
+    const Pts q = select_min_unpruned(4, pm, [&](int i) { return bl_part(pbx, tbx, hl, hw, pl, tl, hll, i); });
+    return bl_finish(pbx, hollow, pl, q, dmin, w);
+}
+#endif  // VMAS_PHYS_GRAD
 
 // TorchUtils.rotate_vector (utils.py:176-191) with precomputed cos/sin of the angle
 VHD V2 rotate(V2 v, Real c, Real s) { return mk(v.x * c - v.y * s, v.x * s + v.y * c); }
