@@ -43,8 +43,9 @@ extern "C" {
  * vmas_copy_spans; VMAS_COPY_MAX_SPANS 160
  * v4: VmasSpawnTargetsIO max_tries / backup; vmas_uniform_columns_snap
  * v5: VmasSpawnTargetsIO scratch / scratch_words (the windowed respawn), vmas_spawn_scratch_words;
- *     the fused programs' out_delta (direct outputs) and VMAS_COPY_STORE64 spans */
-#define VMAS_ABI_VERSION 6
+ *     the fused programs' out_delta (direct outputs) and VMAS_COPY_STORE64 spans
+ * v7: VmasDiscreteActionRef, vmas_apply_discrete_actions / _launch */
+#define VMAS_ABI_VERSION 7
 
 /* error codes */
 #define VMAS_OK 0
@@ -337,6 +338,46 @@ int32_t vmas_apply_actions_launch(int32_t device, int32_t batch, const VmasActio
                                   int32_t n_refs, float* out, uint32_t* seq, void* stream);
 int32_t vmas_apply_actions_flags(int32_t device, uint32_t seq, int32_t n_refs, uint8_t* flags,
                                  void* stream);
+
+/* Discrete actions of Environment._set_action (environment.py:615-760, continuous_actions=False)
+ * for all agents in one pass (csrc/vmas_actions.hip), the no-communication case.  Per agent i and
+ * env b the action is either one column holding the index into the cartesian product of the
+ * components (flat != 0; decoded as flat // prod(nvec[c+1:]) % nvec[c]) or one column per
+ * component.  Component c with n = nvec[c] values: in range when 0 <= a < n; for odd n, 0 -> n/2
+ * and 0 < a <= n/2 -> a - 1; then u[b, c] = ((a / (n - 1)) * (2 * u_range[c]) - u_range[c]) *
+ * u_mult[c], every operation rounded to fp32 on its own, written to out[out_offset + b*n_phys + c];
+ * columns n_comp <= c < n_phys get 0 * u_mult[c].  mode selects the division: 0 divides, 1
+ * multiplies by the fp32 reciprocal of n - 1 (what a torch build does on its device is probed by
+ * the caller).  flags[2*i] = any NaN in the agent's action (float32 actions only), flags[2*i+1] =
+ * something the fused arithmetic does not cover: a value out of range or, for a float32 flat
+ * index, one that is not a whole number (the caller then takes the reference's per-agent path,
+ * which raises or not as the reference does).  u is written for every env even when a flag is
+ * set.  `flags` is a HOST array, published as vmas_apply_actions publishes its flags; device < 0
+ * runs the host backend. */
+#define VMAS_DISCRETE_MAX_COMPONENTS 8
+#define VMAS_DISCRETE_INT64 0
+#define VMAS_DISCRETE_INT32 1
+#define VMAS_DISCRETE_FLOAT32 2
+typedef struct VmasDiscreteActionRef {
+    const void* a;        /* [B, flat ? 1 : n_comp] action tensor (any strides) */
+    const float* u_range; /* [n_phys] u_range_tensor on the same device */
+    const float* u_mult;  /* [n_phys] u_multiplier_tensor on the same device */
+    int64_t out_offset;   /* floats into out of this agent's [B, n_phys] u */
+    int64_t s0, s1;       /* element strides of a */
+    int32_t dtype;        /* VMAS_DISCRETE_INT64 / _INT32 / _FLOAT32 */
+    int32_t flat;
+    int32_t n_comp;       /* 1 .. VMAS_DISCRETE_MAX_COMPONENTS, <= n_phys */
+    int32_t n_phys;       /* action_size, <= VMAS_DISCRETE_MAX_COMPONENTS */
+    int32_t nvec[VMAS_DISCRETE_MAX_COMPONENTS]; /* each in [2, 2^24]; their product <= 2^24 when flat */
+} VmasDiscreteActionRef;
+
+int32_t vmas_apply_discrete_actions(int32_t device, int32_t batch, const VmasDiscreteActionRef* refs,
+                                    int32_t n_refs, float* out, int32_t mode, uint8_t* flags, void* stream);
+/* The launch half of the split (GPU only, n_refs <= 8); vmas_apply_actions_flags is the other
+ * half: both kernels share the sequence counter and the publish word. */
+int32_t vmas_apply_discrete_actions_launch(int32_t device, int32_t batch, const VmasDiscreteActionRef* refs,
+                                           int32_t n_refs, float* out, int32_t mode, uint32_t* seq,
+                                           void* stream);
 
 /* Random actions (Environment.get_random_actions, environment.py:524-606): the uniform_ draws
  * of every agent's action columns in one launch (csrc/vmas_actions.hip).  Column i gets

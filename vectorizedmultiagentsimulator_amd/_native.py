@@ -19,7 +19,7 @@ LIB_PATH = Path(os.environ.get("VMAS_LIB_PATH") or Path(__file__).resolve().pare
 
 # ------------------------------------------------------------------------------------------------
 # constants mirrored from include/vmas_mi355x.h
-VMAS_ABI_VERSION = 6
+VMAS_ABI_VERSION = 7
 VMAS_SPHERE, VMAS_BOX, VMAS_LINE = 0, 1, 2
 (
     VMAS_PAIR_JOINT,
@@ -97,6 +97,8 @@ EXPORTED_SYMBOLS = (
     "vmas_apply_actions",
     "vmas_apply_actions_launch",
     "vmas_apply_actions_flags",
+    "vmas_apply_discrete_actions",
+    "vmas_apply_discrete_actions_launch",
     "vmas_uniform_columns",
     "vmas_uniform_columns_snap",
     "vmas_copy_spans_draw",
@@ -506,12 +508,30 @@ ACTION_APPLY_REF_DTYPE = np.dtype(
         ("pad", "<i4"),
     ]
 )
+DISCRETE_MAX_COMPONENTS = 8
+DISCRETE_INT64, DISCRETE_INT32, DISCRETE_FLOAT32 = 0, 1, 2
+DISCRETE_ACTION_REF_DTYPE = np.dtype(
+    [
+        ("a", "<u8"),
+        ("u_range", "<u8"),
+        ("u_mult", "<u8"),
+        ("out_offset", "<i8"),
+        ("s0", "<i8"),
+        ("s1", "<i8"),
+        ("dtype", "<i4"),
+        ("flat", "<i4"),
+        ("n_comp", "<i4"),
+        ("n_phys", "<i4"),
+        ("nvec", "<i4", (DISCRETE_MAX_COMPONENTS,)),
+    ]
+)
 UNIFORM_COLUMN_DTYPE = np.dtype([("out", "<u8"), ("stride", "<i8"), ("from_", "<f4"), ("to", "<f4"), ("offset", "<u8"),
                                  ("u_out", "<u8"), ("u_stride", "<i8"), ("u_range", "<f4"), ("u_mult", "<f4"),
                                  ("u_clamp", "<i4"), ("pad", "<i4")])
 assert UNIFORM_COLUMN_DTYPE.itemsize == 64
 assert ACTION_REF_DTYPE.itemsize == 40
 assert ACTION_APPLY_REF_DTYPE.itemsize == 56
+assert DISCRETE_ACTION_REF_DTYPE.itemsize == 96
 assert ENTITY_IO_DTYPE.itemsize == 72
 assert AGENT_IO_DTYPE.itemsize == 32
 assert JOINT_IO_DTYPE.itemsize == 16
@@ -631,6 +651,10 @@ def load_library(path: os.PathLike | str | None = None) -> ctypes.CDLL:
     lib.vmas_apply_actions_launch.argtypes = [_i32, _i32, _vp, _i32, _vp, ctypes.POINTER(ctypes.c_uint32), _vp]
     lib.vmas_apply_actions_flags.restype = _i32
     lib.vmas_apply_actions_flags.argtypes = [_i32, ctypes.c_uint32, _i32, _vp, _vp]
+    lib.vmas_apply_discrete_actions.restype = _i32
+    lib.vmas_apply_discrete_actions.argtypes = [_i32, _i32, _vp, _i32, _vp, _i32, _vp, _vp]
+    lib.vmas_apply_discrete_actions_launch.restype = _i32
+    lib.vmas_apply_discrete_actions_launch.argtypes = [_i32, _i32, _vp, _i32, _vp, _i32, ctypes.POINTER(ctypes.c_uint32), _vp]
     lib.vmas_uniform_columns.restype = _i32
     lib.vmas_uniform_columns.argtypes = [_i32, ctypes.c_int64, _vp, _i32, ctypes.c_uint64, ctypes.c_uint64, _i32,
                                          ctypes.POINTER(ctypes.c_uint64), _vp]

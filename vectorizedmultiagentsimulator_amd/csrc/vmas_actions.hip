@@ -1,4 +1,5 @@
-// vmas_actions.hip -- the continuous-action side of Environment.step for every agent in one pass
+// vmas_actions.hip -- the action side of Environment.step for every agent in one pass (continuous
+// actions first; the discrete ones further down: k_apply_discrete_actions)
 // (reference vmas/simulator/environment/environment.py:615-709, _set_action, continuous actions
 // without communication): NaN check (621-623), optional clamp to u_range (636-640), range check
 // (651-655) and u = physical * u_multiplier (709), gfx950 kernel + host backend + C ABI.
@@ -18,6 +19,7 @@
 
 #include <cmath>
 #include <mutex>
+#include <type_traits>
 
 #include <rocrand/rocrand_philox4x32_10.h>
 
@@ -68,6 +70,43 @@ __device__ __forceinline__ bool arrive(uint32_t* counter, uint32_t i, uint32_t n
     return __hip_atomic_fetch_add(&counter[0], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == n_top - 1u;
 }
 
+// The end of an action kernel: workgroup blockIdx.x of ref's gx stores its two flag bits into its
+// slot and arrives; the last of the n * gx workgroups ORs every slot, publishes seq << 32 | flags
+// and clears the counters for the next launch.  Shared by the continuous and the discrete kernel:
+// one sequence counter and one publish word serve both (vmas_apply_actions_flags waits on either).
+__device__ __forceinline__ void publish_flags(uint32_t* slots, uint32_t* counter, uint64_t* hsig, uint32_t seq, int gx,
+                                              int n, int ref, bool nan_seen, bool oor) {
+    __shared__ uint32_t bits;
+    __shared__ bool last;
+    if (threadIdx.x == 0) bits = 0u;
+    __syncthreads();
+    const uint32_t mine = (__any(nan_seen) ? 1u : 0u) | (__any(oor) ? 2u : 0u);
+    if ((threadIdx.x & 63) == 0 && mine) atomicOr(&bits, mine << (2 * ref));
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        __hip_atomic_store(&slots[ref * kMaxBlocksPerRef + blockIdx.x], bits, __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_AGENT);
+        __builtin_amdgcn_s_waitcnt(0);  // the slot store has completed before the arrival
+        last = arrive(counter, (uint32_t)(ref * gx + (int)blockIdx.x), (uint32_t)(gx * n));
+    }
+    __syncthreads();
+    if (!last) return;
+    // the last workgroup: OR every slot, publish, clear the counter for the next call
+    uint32_t f = 0u;
+    for (int i = threadIdx.x; i < gx * n; i += kThreads) {
+        const int rf = i / gx, bx = i - rf * gx;
+        f |= __hip_atomic_load(&slots[rf * kMaxBlocksPerRef + bx], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) bits = 0u;
+    __syncthreads();
+    if (f) atomicOr(&bits, f);
+    __syncthreads();
+    if (threadIdx.x <= kShards) __hip_atomic_store(&counter[32 * threadIdx.x], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (threadIdx.x == 0)
+        __hip_atomic_store(hsig, ((uint64_t)seq << 32) | bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
 __global__ void __launch_bounds__(kThreads) k_apply_actions(ApplyArgs a) {
     const int ref = blockIdx.y;
     const VmasActionApplyRef& r = a.r[ref];
@@ -78,35 +117,7 @@ __global__ void __launch_bounds__(kThreads) k_apply_actions(ApplyArgs a) {
         const int b = idx / r.n_cols, c = idx - b * r.n_cols;
         apply_one(r, a.out, b, c, nan_seen, oor);
     }
-    __shared__ uint32_t bits;
-    __shared__ bool last;
-    if (threadIdx.x == 0) bits = 0u;
-    __syncthreads();
-    const uint32_t mine = (__any(nan_seen) ? 1u : 0u) | (__any(oor) ? 2u : 0u);
-    if ((threadIdx.x & 63) == 0 && mine) atomicOr(&bits, mine << (2 * ref));
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        __hip_atomic_store(&a.slots[ref * kMaxBlocksPerRef + blockIdx.x], bits, __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_AGENT);
-        __builtin_amdgcn_s_waitcnt(0);  // the slot store has completed before the arrival
-        last = arrive(a.counter, (uint32_t)(ref * a.gx + (int)blockIdx.x), (uint32_t)(a.gx * a.n));
-    }
-    __syncthreads();
-    if (!last) return;
-    // the last workgroup: OR every slot, publish, clear the counter for the next call
-    uint32_t f = 0u;
-    for (int i = threadIdx.x; i < a.gx * a.n; i += kThreads) {
-        const int rf = i / a.gx, bx = i - rf * a.gx;
-        f |= __hip_atomic_load(&a.slots[rf * kMaxBlocksPerRef + bx], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) bits = 0u;
-    __syncthreads();
-    if (f) atomicOr(&bits, f);
-    __syncthreads();
-    if (threadIdx.x <= kShards) __hip_atomic_store(&a.counter[32 * threadIdx.x], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (threadIdx.x == 0)
-        __hip_atomic_store(a.hsig, ((uint64_t)a.seq << 32) | bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    publish_flags(a.slots, a.counter, a.hsig, a.seq, a.gx, a.n, ref, nan_seen, oor);
 }
 
 struct DevState {
@@ -150,6 +161,153 @@ uint32_t launch_apply(DevState& d, int batch, const VmasActionApplyRef* refs, in
     a.n = n;
     a.gx = gx;
     hipLaunchKernelGGL(k_apply_actions, dim3(gx, n), dim3(kThreads), 0, st, a);
+    return a.seq;
+}
+
+// ---- discrete actions: every agent's decode + mapping to u in one launch ------------------------
+// (reference environment.py:667-706, _set_action with continuous_actions=False and no
+// communication: per agent a zeros tensor, the flat index decoded by a // % stack chain, and per
+// component one range assert -- a host wait --, two masked writes for odd n and four element-wise
+// kernels.)  One thread per env row: a flat index yields every component of its row.  The loops
+// over components are unrolled over the fixed maximum, so nothing is indexed dynamically (no
+// scratch); what bounds them (n_comp, n_phys, nvec) is uniform per workgroup.
+constexpr int kMaxComp = VMAS_DISCRETE_MAX_COMPONENTS;
+
+struct DiscreteArgs {
+    VmasDiscreteActionRef r[kMaxRefsPerLaunch];
+    float* out;
+    uint32_t* slots;
+    uint32_t* counter;
+    uint64_t* hsig;
+    uint32_t seq;
+    int B, n, gx, mode;
+};
+
+// One env row of one agent.  Integer actions: "some component out of [0, n)" is "flat outside
+// [0, prod(nvec))", one compare, and the decode runs in 32 bits (mixed radix from the last
+// component: the same digits as the reference's // % chain for an index in range).  A float32 flat
+// index is decoded only when it is a whole number in range (then exact in fp32 and as an int);
+// anything else sets the range flag and the caller takes the reference's own float arithmetic.
+// float32 components are mapped in fp32 as the reference maps them, fractional values included.
+// The four roundings of u stay separate (torch runs them as four kernels): no contraction.
+// (integer actions share one instantiation: the two widths differ in the load alone)
+template <bool kFloat>
+__host__ __device__ inline void discrete_row(const VmasDiscreteActionRef& r, float* out, long b, int mode,
+                                             bool& nan_seen, bool& oor) {
+#pragma clang fp contract(off)
+    using T = typename std::conditional<kFloat, float, int64_t>::type;
+    const long row = b * r.s0;
+    auto at = [&r](long i) -> T {
+        if constexpr (kFloat) return ((const float*)r.a)[i];
+        return r.dtype == VMAS_DISCRETE_INT64 ? ((const int64_t*)r.a)[i] : (int64_t)((const int32_t*)r.a)[i];
+    };
+    uint32_t comp[kMaxComp] = {};
+    if (r.flat) {
+        int64_t prod = 1;
+#pragma unroll
+        for (int c = 0; c < kMaxComp; ++c)
+            if (c < r.n_comp) prod *= r.nvec[c];
+        const T v = at(row);
+        bool ok;
+        if constexpr (kFloat) {
+            nan_seen |= (v != v);
+            ok = v >= (T)0 && v < (T)prod && v == floorf(v);
+        } else {
+            ok = v >= (T)0 && (int64_t)v < prod;
+        }
+        oor |= !ok;
+        uint32_t idx = ok ? (uint32_t)v : 0u;
+#pragma unroll
+        for (int c = kMaxComp - 1; c >= 0; --c) {
+            if (c < r.n_comp) {
+                const uint32_t n = (uint32_t)r.nvec[c], q = idx / n;
+                comp[c] = idx - q * n;
+                idx = q;
+            }
+        }
+    }
+    float* o = out + r.out_offset + b * r.n_phys;
+#pragma unroll
+    for (int c = 0; c < kMaxComp; ++c) {
+        if (c >= r.n_phys) continue;
+        float u = 0.0f;
+        if (c < r.n_comp) {
+            const int n = r.nvec[c];
+            float x;
+            if (r.flat) {
+                x = (float)comp[c];
+            } else {
+                const T v = at(row + c * r.s1);
+                if constexpr (kFloat) nan_seen |= (v != v);
+                const bool ok = v >= (T)0 && v < (T)n;
+                oor |= !ok;
+                x = ok ? (float)v : 0.0f;
+            }
+            if (n & 1) {  // odd n: action 0 is u = 0 (swapped with the middle value)
+                const float half = (float)(n / 2);
+                if (x == 0.0f)
+                    x = half;
+                else if (x > 0.0f && x <= half)
+                    x = x - 1.0f;
+            }
+            const float den = (float)(n - 1), um = r.u_range[c];
+            const float q = mode ? x * (1.0f / den) : x / den;
+            const float s = q * (2.0f * um);
+            u = s - um;
+        }
+        o[c] = u * r.u_mult[c];
+    }
+}
+
+template <bool kFloat>
+__device__ __forceinline__ void discrete_rows(const DiscreteArgs& a, const VmasDiscreteActionRef& r, bool& nan_seen,
+                                              bool& oor) {
+    const int stride = (int)gridDim.x * kThreads;  // (B + stride < 2^31: checked by the host)
+    for (int b = (int)blockIdx.x * kThreads + (int)threadIdx.x; b < a.B; b += stride)
+        discrete_row<kFloat>(r, a.out, b, a.mode, nan_seen, oor);
+}
+
+__global__ void __launch_bounds__(kThreads) k_apply_discrete_actions(DiscreteArgs a) {
+    const int ref = blockIdx.y;
+    const VmasDiscreteActionRef& r = a.r[ref];
+    bool nan_seen = false, oor = false;
+    if (r.dtype == VMAS_DISCRETE_FLOAT32)
+        discrete_rows<true>(a, r, nan_seen, oor);
+    else
+        discrete_rows<false>(a, r, nan_seen, oor);
+    publish_flags(a.slots, a.counter, a.hsig, a.seq, a.gx, a.n, ref, nan_seen, oor);
+}
+
+const char* discrete_ref_error(int batch, const VmasDiscreteActionRef& r) {
+    if (!r.a || !r.u_range || !r.u_mult || r.out_offset < 0) return "null pointer or negative offset";
+    if (r.dtype < VMAS_DISCRETE_INT64 || r.dtype > VMAS_DISCRETE_FLOAT32) return "dtype";
+    if (r.n_comp < 1 || r.n_comp > kMaxComp || r.n_phys < r.n_comp || r.n_phys > kMaxComp) return "component count";
+    if (batch > INT32_MAX - kMaxBlocksPerRef * kThreads) return "batch";
+    int64_t prod = 1;
+    for (int c = 0; c < r.n_comp; ++c) {
+        if (r.nvec[c] < 2 || r.nvec[c] > (1 << 24)) return "nvec";
+        prod *= r.nvec[c];
+        if (r.flat && prod > (1 << 24)) return "product of nvec";
+    }
+    return nullptr;
+}
+
+uint32_t launch_discrete(DevState& d, int batch, const VmasDiscreteActionRef* refs, int n, float* out, int mode,
+                         hipStream_t st) {
+    DiscreteArgs a{};
+    for (int i = 0; i < n; ++i) a.r[i] = refs[i];
+    const int gx = std::max(1, std::min(kMaxBlocksPerRef, (batch + kThreads - 1) / kThreads));
+    a.out = out;
+    a.slots = d.slots;
+    a.counter = d.counter;
+    a.hsig = d.dsig;
+    a.seq = ++d.seq;
+    if (a.seq == 0u) a.seq = ++d.seq;  // 0 is the "nothing published" value
+    a.B = batch;
+    a.n = n;
+    a.gx = gx;
+    a.mode = mode;
+    hipLaunchKernelGGL(k_apply_discrete_actions, dim3(gx, n), dim3(kThreads), 0, st, a);
     return a.seq;
 }
 
@@ -325,6 +483,69 @@ int32_t vmas_apply_actions(int32_t device, int32_t batch, const VmasActionApplyR
     for (int first = 0; first < n_refs; first += kMaxRefsPerLaunch) {
         const int n = std::min(kMaxRefsPerLaunch, n_refs - first);
         const uint32_t seq = launch_apply(d, batch, refs + first, n, out, st);
+        VMAS_AUX_HIP(hipGetLastError());
+        uint64_t v = 0;
+        if (int32_t rc = vmas_aux::wait_host_word64(d.hsig, seq, &v, st)) return rc;
+        for (int i = 0; i < n; ++i) {
+            flags[2 * (first + i)] = (v >> (2 * i)) & 1u;
+            flags[2 * (first + i) + 1] = (v >> (2 * i + 1)) & 1u;
+        }
+    }
+    return VMAS_OK;
+}
+
+int32_t vmas_apply_discrete_actions_launch(int32_t device, int32_t batch, const VmasDiscreteActionRef* refs,
+                                           int32_t n_refs, float* out, int32_t mode, uint32_t* seq, void* stream) {
+    if (device < 0 || device >= 64 || n_refs <= 0 || n_refs > kMaxRefsPerLaunch || batch <= 0 || !refs || !out ||
+        !seq || mode < 0 || mode > 1)
+        return vmas_aux::fail(VMAS_E_INVALID, "vmas_apply_discrete_actions_launch: bad arguments");
+    for (int i = 0; i < n_refs; ++i)
+        if (const char* why = discrete_ref_error(batch, refs[i]))
+            return vmas_aux::fail(VMAS_E_INVALID, "vmas_apply_discrete_actions_launch: bad ref %d (%s)", i, why);
+    std::lock_guard<std::mutex> lk(g_mu);
+    int cur = -1;
+    VMAS_AUX_HIP(hipGetDevice(&cur));
+    if (cur != device) VMAS_AUX_HIP(hipSetDevice(device));
+    DevState& d = g_dev[device];
+    if (int32_t rc = dev_init(d)) return rc;
+    *seq = launch_discrete(d, batch, refs, n_refs, out, mode, (hipStream_t)stream);
+    VMAS_AUX_HIP(hipGetLastError());
+    return VMAS_OK;
+}
+
+int32_t vmas_apply_discrete_actions(int32_t device, int32_t batch, const VmasDiscreteActionRef* refs, int32_t n_refs,
+                                    float* out, int32_t mode, uint8_t* flags, void* stream) {
+    if (n_refs <= 0 || batch <= 0) return VMAS_OK;
+    if (!refs || !out || !flags || mode < 0 || mode > 1)
+        return vmas_aux::fail(VMAS_E_INVALID, "vmas_apply_discrete_actions: bad arguments");
+    for (int i = 0; i < n_refs; ++i)
+        if (const char* why = discrete_ref_error(batch, refs[i]))
+            return vmas_aux::fail(VMAS_E_INVALID, "vmas_apply_discrete_actions: bad ref %d (%s)", i, why);
+    if (device < 0) {
+        for (int i = 0; i < n_refs; ++i) {
+            bool nan_seen = false, oor = false;
+            for (int b = 0; b < batch; ++b) {
+                if (refs[i].dtype == VMAS_DISCRETE_FLOAT32)
+                    discrete_row<true>(refs[i], out, b, mode, nan_seen, oor);
+                else
+                    discrete_row<false>(refs[i], out, b, mode, nan_seen, oor);
+            }
+            flags[2 * i] = nan_seen;
+            flags[2 * i + 1] = oor;
+        }
+        return VMAS_OK;
+    }
+    if (device >= 64) return vmas_aux::fail(VMAS_E_INVALID, "vmas_apply_discrete_actions: device %d", device);
+    std::lock_guard<std::mutex> lk(g_mu);
+    int cur = -1;
+    VMAS_AUX_HIP(hipGetDevice(&cur));
+    if (cur != device) VMAS_AUX_HIP(hipSetDevice(device));
+    DevState& d = g_dev[device];
+    if (int32_t rc = dev_init(d)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    for (int first = 0; first < n_refs; first += kMaxRefsPerLaunch) {
+        const int n = std::min(kMaxRefsPerLaunch, n_refs - first);
+        const uint32_t seq = launch_discrete(d, batch, refs + first, n, out, mode, st);
         VMAS_AUX_HIP(hipGetLastError());
         uint64_t v = 0;
         if (int32_t rc = vmas_aux::wait_host_word64(d.hsig, seq, &v, st)) return rc;

@@ -11,7 +11,9 @@ scenario's rewards / observations / infos / dones -- into ONE HIP graph
 What a replay must honour, and how:
   * Actions.  The native action kernel (one launch, one host wait for the NaN / range flags, as
     the reference's asserts) runs eagerly before the replay and writes every agent's ``u`` into
-    ONE persistent buffer, so the captured program reads the current actions.
+    ONE persistent buffer, so the captured program reads the current actions.  Continuous actions
+    (vmas_apply_actions) and discrete ones (vmas_apply_discrete_actions: flat or multi-discrete)
+    fill the same buffer with the same layout; nothing below depends on which.
   * State carried across steps by re-binding.  The reference creates new tensors every step
     (integration, core.py:2866-2907; scenario attributes such as balance's ``global_shaping``).
     A captured program reads the tensors that were bound when it was captured (X) and writes
@@ -36,7 +38,8 @@ What a replay must honour, and how:
     generator -- and raises from the same step() call.
   * What cannot be captured -- a host sync inside the step (``.item()``, ``bool(t.any())``,
     the spawn sampler's rejection loop), a host-to-device copy
-    of pageable memory, discrete or communication actions -- makes the capture fail; the
+    of pageable memory -- makes the capture fail (communication actions, which take the per-agent
+    action path, keep the env eager without an attempt); the
     simulator's objects are rolled back (nothing ran: capture only records) and the env stays
     eager.  ``env.graph_status`` says which.
   * Per-step host state.  A replay runs no Python, so host state the step changes would be
