@@ -7,6 +7,8 @@ import torch
 
 from vectorizedmultiagentsimulator_amd import make_env
 
+from tests._action_chunks import late_chunk_failure
+
 
 def _pair(device, **kw):
     # (eager steps: the action paths themselves; graph mode's own use of them is tests/test_graph.py's)
@@ -67,6 +69,13 @@ def test_fused_actions_failure_side_effects(bad):
         assert torch.equal(fused.agents[i].action.u, before[i])
 
 
+@pytest.mark.parametrize("bad", ["nan", "range"])
+def test_fused_actions_failure_in_a_later_chunk(bad):
+    """9 agents: the failing one is past the first 8 refs (on the host backend, past the first 16
+    flag bytes)."""
+    late_chunk_failure("cpu", bad, continuous=True)
+
+
 def test_fused_actions_noise_draws_match():
     fused, ref = _pair("cpu")
     for env in (fused, ref):
@@ -86,6 +95,17 @@ def test_fused_actions_noise_draws_match():
 def test_fused_actions_skipped_for_other_dtypes():
     env = make_env("balance", num_envs=8, seed=0, n_agents=2)
     assert env._apply_continuous_actions([torch.zeros(8, 2, dtype=torch.float64)] * 2) is False
+
+
+def test_fused_actions_refusal_names_its_reason():
+    env = make_env("balance", num_envs=8, seed=0, n_agents=2)
+    env.agents[1].action._u_range_tensor = env.agents[1].action.u_range_tensor.double()
+    assert env._apply_continuous_actions([torch.zeros(8, 2)] * 2) is False
+    assert env._apply_cache.refusal == "u_range / u_multiplier are not float32"
+    env = make_env("features", num_envs=8, seed=0)
+    assert env.world.dim_c > 0 and any(not a.silent for a in env.agents)
+    assert env._apply_continuous_actions(env.get_random_actions()) is False
+    assert "communication actions" in env._apply_cache.refusal
 
 
 @pytest.mark.gpu
@@ -108,3 +128,10 @@ def test_fused_actions_failure_gpu(gpu_device):
     with pytest.raises(AssertionError, match="out of its range"):
         env.step(bad)
     env.step(acts)  # the device flags were reset: a valid step passes again
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("bad", ["nan", "range"])
+def test_fused_actions_failure_in_a_later_chunk_gpu(gpu_device, bad):
+    """9 agents are two launches (8 + 1 refs): the flag is set in the second one."""
+    late_chunk_failure(gpu_device, bad, continuous=True)

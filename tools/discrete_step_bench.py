@@ -46,7 +46,7 @@ def run(args, multi: bool) -> dict:
         "env_steps_per_s": round(args.envs * args.steps / dev),
         "graph_status": getattr(env, "graph_status", "off"),
         "graph_reason": getattr(env, "graph_reason", ""),
-        "fused_actions": bool(getattr(env, "_apply_cache", None) and env._apply_cache[1] is not None),
+        "fused_actions": getattr(getattr(env, "_apply_cache", None), "refusal", "") is None,
     }
 
 

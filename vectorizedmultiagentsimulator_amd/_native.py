@@ -311,6 +311,16 @@ def _raw_stream(index):
     return torch._C._cuda_getCurrentRawStream(index)
 
 
+def launch_args(device):
+    """(device index for the library, stream pointer) of a torch device; (-1, None): the host backend."""
+    if device.type != "cuda":
+        return -1, None
+    import torch
+
+    idx = device.index if device.index is not None else torch.cuda.current_device()
+    return idx, stream_ptr(idx)
+
+
 def copy_table(device_index: int, table: np.ndarray, lo: int, hi: int, stream) -> None:
     """One native launch (vmas_copy_spans) for rows lo..hi of a COPY_SPAN_DTYPE table."""
     copy_table_at(device_index, table.ctypes.data, lo, hi, stream)

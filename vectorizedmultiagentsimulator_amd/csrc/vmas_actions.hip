@@ -141,16 +141,10 @@ int32_t dev_init(DevState& d) {
     return VMAS_OK;
 }
 
-// One launch over n <= kMaxRefsPerLaunch refs; returns the sequence number it publishes.
-uint32_t launch_apply(DevState& d, int batch, const VmasActionApplyRef* refs, int n, float* out, hipStream_t st) {
-    ApplyArgs a{};
-    long max_elems = 0;
-    for (int i = 0; i < n; ++i) {
-        a.r[i] = refs[i];
-        max_elems = std::max(max_elems, (long)batch * refs[i].n_cols);
-    }
-    const int gx = (int)std::max(1L, std::min((long)kMaxBlocksPerRef, (max_elems + kThreads * kPerThread - 1) /
-                                                                           (kThreads * kPerThread)));
+// What the arguments of every action launch share (ApplyArgs / DiscreteArgs): the device's flag
+// buffers, the next sequence number and the grid.  Returns the sequence number the launch publishes.
+template <typename Args>
+uint32_t stamp(Args& a, DevState& d, int batch, int n, int gx, float* out) {
     a.out = out;
     a.slots = d.slots;
     a.counter = d.counter;
@@ -160,9 +154,40 @@ uint32_t launch_apply(DevState& d, int batch, const VmasActionApplyRef* refs, in
     a.B = batch;
     a.n = n;
     a.gx = gx;
-    hipLaunchKernelGGL(k_apply_actions, dim3(gx, n), dim3(kThreads), 0, st, a);
     return a.seq;
 }
+
+// A kind of action (continuous below, discrete further down) is what apply_blocking / apply_launch
+// need beside the shared body: its ref type, whether its own arguments are valid, what is wrong
+// with a ref (nullptr: nothing; "" : nothing to add to its index), one ref on the host backend, and
+// one launch over n <= kMaxRefsPerLaunch refs, which returns the sequence number it publishes.
+struct ContinuousKind {
+    using Ref = VmasActionApplyRef;
+    static constexpr const char* kBadBlocking = "null argument";  // (what the blocking entry point answers)
+    bool ok() const { return true; }
+    const char* ref_error(int batch, const Ref& r) const {
+        const bool bad = !r.u || !r.u_range || !r.u_mult || r.n_phys > r.n_cols || r.n_phys < 0 || r.out_offset < 0 ||
+                         (long)batch * r.n_cols > INT32_MAX;
+        return bad ? "" : nullptr;
+    }
+    void host_ref(const Ref& r, float* out, int batch, bool& nan_seen, bool& oor) const {
+        for (int b = 0; b < batch; ++b)
+            for (int c = 0; c < r.n_cols; ++c) apply_one(r, out, b, c, nan_seen, oor);
+    }
+    uint32_t launch(DevState& d, int batch, const Ref* refs, int n, float* out, hipStream_t st) const {
+        ApplyArgs a{};
+        long max_elems = 0;
+        for (int i = 0; i < n; ++i) {
+            a.r[i] = refs[i];
+            max_elems = std::max(max_elems, (long)batch * refs[i].n_cols);
+        }
+        const int gx = (int)std::max(1L, std::min((long)kMaxBlocksPerRef, (max_elems + kThreads * kPerThread - 1) /
+                                                                               (kThreads * kPerThread)));
+        const uint32_t seq = stamp(a, d, batch, n, gx, out);
+        hipLaunchKernelGGL(k_apply_actions, dim3(gx, n), dim3(kThreads), 0, st, a);
+        return seq;
+    }
+};
 
 // ---- discrete actions: every agent's decode + mapping to u in one launch ------------------------
 // (reference environment.py:667-706, _set_action with continuous_actions=False and no
@@ -278,37 +303,114 @@ __global__ void __launch_bounds__(kThreads) k_apply_discrete_actions(DiscreteArg
     publish_flags(a.slots, a.counter, a.hsig, a.seq, a.gx, a.n, ref, nan_seen, oor);
 }
 
-const char* discrete_ref_error(int batch, const VmasDiscreteActionRef& r) {
-    if (!r.a || !r.u_range || !r.u_mult || r.out_offset < 0) return "null pointer or negative offset";
-    if (r.dtype < VMAS_DISCRETE_INT64 || r.dtype > VMAS_DISCRETE_FLOAT32) return "dtype";
-    if (r.n_comp < 1 || r.n_comp > kMaxComp || r.n_phys < r.n_comp || r.n_phys > kMaxComp) return "component count";
-    if (batch > INT32_MAX - kMaxBlocksPerRef * kThreads) return "batch";
-    int64_t prod = 1;
-    for (int c = 0; c < r.n_comp; ++c) {
-        if (r.nvec[c] < 2 || r.nvec[c] > (1 << 24)) return "nvec";
-        prod *= r.nvec[c];
-        if (r.flat && prod > (1 << 24)) return "product of nvec";
+struct DiscreteKind {
+    using Ref = VmasDiscreteActionRef;
+    static constexpr const char* kBadBlocking = "bad arguments";
+    int mode;
+    bool ok() const { return mode == 0 || mode == 1; }
+    const char* ref_error(int batch, const Ref& r) const {
+        if (!r.a || !r.u_range || !r.u_mult || r.out_offset < 0) return "null pointer or negative offset";
+        if (r.dtype < VMAS_DISCRETE_INT64 || r.dtype > VMAS_DISCRETE_FLOAT32) return "dtype";
+        if (r.n_comp < 1 || r.n_comp > kMaxComp || r.n_phys < r.n_comp || r.n_phys > kMaxComp) return "component count";
+        if (batch > INT32_MAX - kMaxBlocksPerRef * kThreads) return "batch";
+        int64_t prod = 1;
+        for (int c = 0; c < r.n_comp; ++c) {
+            if (r.nvec[c] < 2 || r.nvec[c] > (1 << 24)) return "nvec";
+            prod *= r.nvec[c];
+            if (r.flat && prod > (1 << 24)) return "product of nvec";
+        }
+        return nullptr;
     }
-    return nullptr;
+    void host_ref(const Ref& r, float* out, int batch, bool& nan_seen, bool& oor) const {
+        for (int b = 0; b < batch; ++b) {
+            if (r.dtype == VMAS_DISCRETE_FLOAT32)
+                discrete_row<true>(r, out, b, mode, nan_seen, oor);
+            else
+                discrete_row<false>(r, out, b, mode, nan_seen, oor);
+        }
+    }
+    uint32_t launch(DevState& d, int batch, const Ref* refs, int n, float* out, hipStream_t st) const {
+        DiscreteArgs a{};
+        for (int i = 0; i < n; ++i) a.r[i] = refs[i];
+        const int gx = std::max(1, std::min(kMaxBlocksPerRef, (batch + kThreads - 1) / kThreads));
+        const uint32_t seq = stamp(a, d, batch, n, gx, out);
+        a.mode = mode;
+        hipLaunchKernelGGL(k_apply_discrete_actions, dim3(gx, n), dim3(kThreads), 0, st, a);
+        return seq;
+    }
+};
+
+// ---- the host side of both kinds -----------------------------------------------------------------
+template <typename Kind>
+int32_t check_refs(const char* name, const Kind& k, int batch, const typename Kind::Ref* refs, int n_refs) {
+    for (int i = 0; i < n_refs; ++i)
+        if (const char* why = k.ref_error(batch, refs[i]))
+            return *why ? vmas_aux::fail(VMAS_E_INVALID, "%s: bad ref %d (%s)", name, i, why)
+                        : vmas_aux::fail(VMAS_E_INVALID, "%s: bad ref %d", name, i);
+    return VMAS_OK;
 }
 
-uint32_t launch_discrete(DevState& d, int batch, const VmasDiscreteActionRef* refs, int n, float* out, int mode,
-                         hipStream_t st) {
-    DiscreteArgs a{};
-    for (int i = 0; i < n; ++i) a.r[i] = refs[i];
-    const int gx = std::max(1, std::min(kMaxBlocksPerRef, (batch + kThreads - 1) / kThreads));
-    a.out = out;
-    a.slots = d.slots;
-    a.counter = d.counter;
-    a.hsig = d.dsig;
-    a.seq = ++d.seq;
-    if (a.seq == 0u) a.seq = ++d.seq;  // 0 is the "nothing published" value
-    a.B = batch;
-    a.n = n;
-    a.gx = gx;
-    a.mode = mode;
-    hipLaunchKernelGGL(k_apply_discrete_actions, dim3(gx, n), dim3(kThreads), 0, st, a);
-    return a.seq;
+// The device's flag state, with the device made current (the caller holds g_mu).
+int32_t enter_device(int device, DevState*& d) {
+    int cur = -1;
+    VMAS_AUX_HIP(hipGetDevice(&cur));
+    if (cur != device) VMAS_AUX_HIP(hipSetDevice(device));
+    d = &g_dev[device];
+    return dev_init(*d);
+}
+
+// A published word's flag bits as two bytes per ref (NaN seen, out of range).
+void unpack_flags(uint64_t v, int n, uint8_t* flags) {
+    for (int i = 0; i < 2 * n; ++i) flags[i] = (v >> i) & 1u;
+}
+
+// Launch only (n_refs <= kMaxRefsPerLaunch): vmas_apply_actions_flags waits for *seq later.
+template <typename Kind>
+int32_t apply_launch(const char* name, const Kind& k, int device, int batch, const typename Kind::Ref* refs, int n_refs,
+                     float* out, uint32_t* seq, void* stream) {
+    if (device < 0 || device >= 64 || n_refs <= 0 || n_refs > kMaxRefsPerLaunch || batch <= 0 || !refs || !out || !seq ||
+        !k.ok())
+        return vmas_aux::fail(VMAS_E_INVALID, "%s: bad arguments", name);
+    if (int32_t rc = check_refs(name, k, batch, refs, n_refs)) return rc;
+    std::lock_guard<std::mutex> lk(g_mu);
+    DevState* d = nullptr;
+    if (int32_t rc = enter_device(device, d)) return rc;
+    *seq = k.launch(*d, batch, refs, n_refs, out, (hipStream_t)stream);
+    VMAS_AUX_HIP(hipGetLastError());
+    return VMAS_OK;
+}
+
+// Any number of refs, flags included: the host backend (device < 0), or launches of at most
+// kMaxRefsPerLaunch refs, each waited for before the next (they share the slots and the word).
+template <typename Kind>
+int32_t apply_blocking(const char* name, const Kind& k, int device, int batch, const typename Kind::Ref* refs,
+                       int n_refs, float* out, uint8_t* flags, void* stream) {
+    if (n_refs <= 0 || batch <= 0) return VMAS_OK;
+    if (!refs || !out || !flags || !k.ok()) return vmas_aux::fail(VMAS_E_INVALID, "%s: %s", name, Kind::kBadBlocking);
+    if (int32_t rc = check_refs(name, k, batch, refs, n_refs)) return rc;
+    if (device < 0) {
+        for (int i = 0; i < n_refs; ++i) {
+            bool nan_seen = false, oor = false;
+            k.host_ref(refs[i], out, batch, nan_seen, oor);
+            flags[2 * i] = nan_seen;
+            flags[2 * i + 1] = oor;
+        }
+        return VMAS_OK;
+    }
+    if (device >= 64) return vmas_aux::fail(VMAS_E_INVALID, "%s: device %d", name, device);
+    std::lock_guard<std::mutex> lk(g_mu);
+    DevState* d = nullptr;
+    if (int32_t rc = enter_device(device, d)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    for (int first = 0; first < n_refs; first += kMaxRefsPerLaunch) {
+        const int n = std::min(kMaxRefsPerLaunch, n_refs - first);
+        const uint32_t seq = k.launch(*d, batch, refs + first, n, out, st);
+        VMAS_AUX_HIP(hipGetLastError());
+        uint64_t v = 0;
+        if (int32_t rc = vmas_aux::wait_host_word64(d->hsig, seq, &v, st)) return rc;
+        unpack_flags(v, n, flags + 2 * first);
+    }
+    return VMAS_OK;
 }
 
 // Deferred assertion of one slot: AND of n condition bytes, published with the slot's next epoch.
@@ -423,21 +525,7 @@ extern "C" {
 
 int32_t vmas_apply_actions_launch(int32_t device, int32_t batch, const VmasActionApplyRef* refs, int32_t n_refs,
                                   float* out, uint32_t* seq, void* stream) {
-    if (device < 0 || device >= 64 || n_refs <= 0 || n_refs > kMaxRefsPerLaunch || batch <= 0 || !refs || !out || !seq)
-        return vmas_aux::fail(VMAS_E_INVALID, "vmas_apply_actions_launch: bad arguments");
-    for (int i = 0; i < n_refs; ++i)
-        if (!refs[i].u || !refs[i].u_range || !refs[i].u_mult || refs[i].n_phys > refs[i].n_cols ||
-            refs[i].n_phys < 0 || refs[i].out_offset < 0 || (long)batch * refs[i].n_cols > INT32_MAX)
-            return vmas_aux::fail(VMAS_E_INVALID, "vmas_apply_actions_launch: bad ref %d", i);
-    std::lock_guard<std::mutex> lk(g_mu);
-    int cur = -1;
-    VMAS_AUX_HIP(hipGetDevice(&cur));
-    if (cur != device) VMAS_AUX_HIP(hipSetDevice(device));
-    DevState& d = g_dev[device];
-    if (int32_t rc = dev_init(d)) return rc;
-    *seq = launch_apply(d, batch, refs, n_refs, out, (hipStream_t)stream);
-    VMAS_AUX_HIP(hipGetLastError());
-    return VMAS_OK;
+    return apply_launch("vmas_apply_actions_launch", ContinuousKind{}, device, batch, refs, n_refs, out, seq, stream);
 }
 
 int32_t vmas_apply_actions_flags(int32_t device, uint32_t seq, int32_t n_refs, uint8_t* flags, void* stream) {
@@ -447,114 +535,25 @@ int32_t vmas_apply_actions_flags(int32_t device, uint32_t seq, int32_t n_refs, u
     if (!d.hsig) return vmas_aux::fail(VMAS_E_INVALID, "vmas_apply_actions_flags: nothing launched");
     uint64_t v = 0;
     if (int32_t rc = vmas_aux::wait_host_word64(d.hsig, seq, &v, (hipStream_t)stream)) return rc;
-    for (int i = 0; i < n_refs; ++i) {
-        flags[2 * i] = (v >> (2 * i)) & 1u;
-        flags[2 * i + 1] = (v >> (2 * i + 1)) & 1u;
-    }
+    unpack_flags(v, n_refs, flags);
     return VMAS_OK;
 }
 
 int32_t vmas_apply_actions(int32_t device, int32_t batch, const VmasActionApplyRef* refs, int32_t n_refs,
                            float* out, uint8_t* flags, void* stream) {
-    if (n_refs <= 0 || batch <= 0) return VMAS_OK;
-    if (!refs || !out || !flags) return vmas_aux::fail(VMAS_E_INVALID, "vmas_apply_actions: null argument");
-    for (int i = 0; i < n_refs; ++i)
-        if (!refs[i].u || !refs[i].u_range || !refs[i].u_mult || refs[i].n_phys > refs[i].n_cols ||
-            refs[i].n_phys < 0 || refs[i].out_offset < 0 || (long)batch * refs[i].n_cols > INT32_MAX)
-            return vmas_aux::fail(VMAS_E_INVALID, "vmas_apply_actions: bad ref %d", i);
-    if (device < 0) {
-        for (int i = 0; i < n_refs; ++i) {
-            bool nan_seen = false, oor = false;
-            for (int b = 0; b < batch; ++b)
-                for (int c = 0; c < refs[i].n_cols; ++c) apply_one(refs[i], out, b, c, nan_seen, oor);
-            flags[2 * i] = nan_seen;
-            flags[2 * i + 1] = oor;
-        }
-        return VMAS_OK;
-    }
-    if (device >= 64) return vmas_aux::fail(VMAS_E_INVALID, "vmas_apply_actions: device %d", device);
-    std::lock_guard<std::mutex> lk(g_mu);
-    int cur = -1;
-    VMAS_AUX_HIP(hipGetDevice(&cur));
-    if (cur != device) VMAS_AUX_HIP(hipSetDevice(device));
-    DevState& d = g_dev[device];
-    if (int32_t rc = dev_init(d)) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    for (int first = 0; first < n_refs; first += kMaxRefsPerLaunch) {
-        const int n = std::min(kMaxRefsPerLaunch, n_refs - first);
-        const uint32_t seq = launch_apply(d, batch, refs + first, n, out, st);
-        VMAS_AUX_HIP(hipGetLastError());
-        uint64_t v = 0;
-        if (int32_t rc = vmas_aux::wait_host_word64(d.hsig, seq, &v, st)) return rc;
-        for (int i = 0; i < n; ++i) {
-            flags[2 * (first + i)] = (v >> (2 * i)) & 1u;
-            flags[2 * (first + i) + 1] = (v >> (2 * i + 1)) & 1u;
-        }
-    }
-    return VMAS_OK;
+    return apply_blocking("vmas_apply_actions", ContinuousKind{}, device, batch, refs, n_refs, out, flags, stream);
 }
 
 int32_t vmas_apply_discrete_actions_launch(int32_t device, int32_t batch, const VmasDiscreteActionRef* refs,
                                            int32_t n_refs, float* out, int32_t mode, uint32_t* seq, void* stream) {
-    if (device < 0 || device >= 64 || n_refs <= 0 || n_refs > kMaxRefsPerLaunch || batch <= 0 || !refs || !out ||
-        !seq || mode < 0 || mode > 1)
-        return vmas_aux::fail(VMAS_E_INVALID, "vmas_apply_discrete_actions_launch: bad arguments");
-    for (int i = 0; i < n_refs; ++i)
-        if (const char* why = discrete_ref_error(batch, refs[i]))
-            return vmas_aux::fail(VMAS_E_INVALID, "vmas_apply_discrete_actions_launch: bad ref %d (%s)", i, why);
-    std::lock_guard<std::mutex> lk(g_mu);
-    int cur = -1;
-    VMAS_AUX_HIP(hipGetDevice(&cur));
-    if (cur != device) VMAS_AUX_HIP(hipSetDevice(device));
-    DevState& d = g_dev[device];
-    if (int32_t rc = dev_init(d)) return rc;
-    *seq = launch_discrete(d, batch, refs, n_refs, out, mode, (hipStream_t)stream);
-    VMAS_AUX_HIP(hipGetLastError());
-    return VMAS_OK;
+    return apply_launch("vmas_apply_discrete_actions_launch", DiscreteKind{mode}, device, batch, refs, n_refs, out, seq,
+                        stream);
 }
 
 int32_t vmas_apply_discrete_actions(int32_t device, int32_t batch, const VmasDiscreteActionRef* refs, int32_t n_refs,
                                     float* out, int32_t mode, uint8_t* flags, void* stream) {
-    if (n_refs <= 0 || batch <= 0) return VMAS_OK;
-    if (!refs || !out || !flags || mode < 0 || mode > 1)
-        return vmas_aux::fail(VMAS_E_INVALID, "vmas_apply_discrete_actions: bad arguments");
-    for (int i = 0; i < n_refs; ++i)
-        if (const char* why = discrete_ref_error(batch, refs[i]))
-            return vmas_aux::fail(VMAS_E_INVALID, "vmas_apply_discrete_actions: bad ref %d (%s)", i, why);
-    if (device < 0) {
-        for (int i = 0; i < n_refs; ++i) {
-            bool nan_seen = false, oor = false;
-            for (int b = 0; b < batch; ++b) {
-                if (refs[i].dtype == VMAS_DISCRETE_FLOAT32)
-                    discrete_row<true>(refs[i], out, b, mode, nan_seen, oor);
-                else
-                    discrete_row<false>(refs[i], out, b, mode, nan_seen, oor);
-            }
-            flags[2 * i] = nan_seen;
-            flags[2 * i + 1] = oor;
-        }
-        return VMAS_OK;
-    }
-    if (device >= 64) return vmas_aux::fail(VMAS_E_INVALID, "vmas_apply_discrete_actions: device %d", device);
-    std::lock_guard<std::mutex> lk(g_mu);
-    int cur = -1;
-    VMAS_AUX_HIP(hipGetDevice(&cur));
-    if (cur != device) VMAS_AUX_HIP(hipSetDevice(device));
-    DevState& d = g_dev[device];
-    if (int32_t rc = dev_init(d)) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    for (int first = 0; first < n_refs; first += kMaxRefsPerLaunch) {
-        const int n = std::min(kMaxRefsPerLaunch, n_refs - first);
-        const uint32_t seq = launch_discrete(d, batch, refs + first, n, out, mode, st);
-        VMAS_AUX_HIP(hipGetLastError());
-        uint64_t v = 0;
-        if (int32_t rc = vmas_aux::wait_host_word64(d.hsig, seq, &v, st)) return rc;
-        for (int i = 0; i < n; ++i) {
-            flags[2 * (first + i)] = (v >> (2 * i)) & 1u;
-            flags[2 * (first + i) + 1] = (v >> (2 * i + 1)) & 1u;
-        }
-    }
-    return VMAS_OK;
+    return apply_blocking("vmas_apply_discrete_actions", DiscreteKind{mode}, device, batch, refs, n_refs, out, flags,
+                          stream);
 }
 
 int32_t vmas_uniform_columns(int32_t device, int64_t numel, const VmasUniformColumn* cols, int32_t n_cols,

@@ -49,21 +49,12 @@ def reference_u(a: torch.Tensor, nvec, u_range: torch.Tensor, u_mult: torch.Tens
     return u
 
 
-def launch_args(device: torch.device):
-    """(device index for the library, stream pointer or None)."""
-    if device.type == "cuda":
-        N = _native()
-        idx = device.index if device.index is not None else torch.cuda.current_device()
-        return idx, N.stream_ptr(idx)
-    return -1, None
-
-
 def mode(device: torch.device) -> Optional[int]:
     key = str(device)
     if key in MODES:
         return MODES[key]
     N = _native()
-    idx, stream = launch_args(device)
+    idx, stream = N.launch_args(device)
     B, K = max(_PROBE_N), N.DISCRETE_MAX_COMPONENTS
     rows = torch.arange(B, dtype=torch.int64).unsqueeze(1)
     r = torch.tensor(_PROBE_RANGE, dtype=torch.float32, device=device)

@@ -619,7 +619,7 @@ class _FreshState:
         pc = env._u_persist
         if not self.persist_items or pc is None:
             return
-        P = pc[1]
+        P = pc.buffer
         live = [(d, k, y) for d, k, y in self.persist_items
                 if d.get(k) is y and y.untyped_storage().data_ptr() == P.untyped_storage().data_ptr()]
         if not live:
@@ -904,11 +904,11 @@ class StepGraph:
             except Exception as ex:  # noqa: BLE001 -- drain every channel, then raise the first
                 err = err or ex
         sp = getattr(self.env, "_spec", None)
-        if sp is not None and sp[3] is None:
+        if sp is not None and sp.offset is None:
             if err is not None or redone or not apply:
                 self.env._spec = None
             else:
-                self.env._spec = sp[:3] + (sp[0][5].get_offset(),) + sp[4:]
+                self.env._spec = sp._replace(offset=sp.plan.gen.get_offset())
         if err is not None:
             raise err
         if redone and out is not None:
@@ -1065,8 +1065,8 @@ class StepGraph:
         self._steps_t = env.steps
         persist = []
         pc = env._u_persist
-        if pc is not None and pc[2] is not None:
-            pkey = _storage_key(pc[1])
+        if pc is not None and pc.views is not None:
+            pkey = _storage_key(pc.buffer)
             for ag in env.world.agents:
                 for o, k in ((ag._action, "_u"), (ag._state, "_force")):
                     t = o.__dict__.get(k)

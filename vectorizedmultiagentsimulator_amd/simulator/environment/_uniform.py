@@ -12,6 +12,7 @@ generator advance -- or returns None (callers then draw with torch).
 from __future__ import annotations
 
 import ctypes
+from collections import namedtuple
 from typing import Any, Dict, Optional
 
 import numpy as np
@@ -27,6 +28,25 @@ def _native():
     from ... import _native as N
 
     return N
+
+
+# Every agent's random-action columns as one launch (Environment._fused_random_actions): the _native
+# module, the UNIFORM_COLUMN_DTYPE table (one row per column) and its address, the columns per agent,
+# device index, mode() of (device, B), the device generator and, for equal widths, each column's
+# byte offset in one [A, B, n] allocation (else None)
+ColumnDrawPlan = namedtuple("ColumnDrawPlan", "N cols widths idx mode gen cols_addr B dev offsets")
+# Environment._uniform_cache: the per-agent column plans the draw plan was built from, the plan
+# (None: the draws keep torch's own calls) and what the key depends on (_uniform_sig)
+DrawCache = namedtuple("DrawCache", "key plan sig", defaults=(None,))
+# the last draw whose applied values are in the persistent action buffer ``buffer``
+Drawn = namedtuple("Drawn", "actions ptrs versions buffer")
+# a draw made ahead by the post-replay launch: the generator state it was made at (offset None
+# until a deferred respawn has left it), its advance and Environment._preapply_tag at the draw
+SpecDraw = namedtuple("SpecDraw", "plan actions seed offset inc tag")
+
+
+def drawn(actions, buffer) -> Drawn:
+    return Drawn(tuple(actions), tuple(o.data_ptr() for o in actions), tuple(o._version for o in actions), buffer)
 
 
 def launch(idx: int, B: int, cols: np.ndarray, mode: int, gen: torch.Generator, cols_addr: Optional[int] = None) -> None:

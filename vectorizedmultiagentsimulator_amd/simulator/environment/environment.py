@@ -13,7 +13,6 @@ Rendering is outside the scope of the MI355X engine.
 from __future__ import annotations
 
 import contextlib
-import ctypes
 import math
 import os
 import random
@@ -24,12 +23,13 @@ import numpy as np
 import torch
 from torch import Tensor
 
+from ... import _native as N
 from .. import core as _core
 from ..core import Agent, TorchVectorizedObject
 from ..scenario import BaseScenario
 from ..utils import AGENT_OBS_TYPE, DEVICE_TYPING, TorchUtils, override
 from . import spaces
-from . import _discrete
+from . import _actions
 from . import _uniform
 from ._rng import numpy_global_rng, python_global_rng
 
@@ -180,12 +180,12 @@ class Environment(TorchVectorizedObject):
         # backward (simulator/_engine.py _StepFn / _RaysFn / _DistFn); the fused scenario programs
         # (no backward) give way to the scenarios' torch programs
         self.world._grad_enabled = bool(grad_enabled)
-        self._apply_cache = None  # see _apply_continuous_actions / _apply_discrete_actions
-        self._u_persist = None  # persistent action buffer of graph mode (see _apply_continuous_actions)
+        self._apply_cache = None  # the _actions.ActionPlan of the last fused apply
+        self._u_persist = None  # _actions.PersistentActions: the action buffer of graph mode
         self._spec_keep = None  # action tensors a speculative action launch reads
         self._draw_plans = {}  # agent -> cached column plan of its random actions
-        self._uniform_cache = None  # see _fused_random_actions
-        self._uniform_host = None  # (column plan, its csrc/vmas_host.cpp UniformDraw)
+        self._uniform_cache = None  # _uniform.DrawCache, see _fused_random_actions
+        self._uniform_host = None  # (column draw plan, its csrc/vmas_host.cpp UniformDraw)
         self._ushadow = _ActionShadow()
         self._spec = None  # a draw made ahead by the post-replay launch (_draw_ahead_plan)
         self._spec_ok = False  # the last step consumed a draw applied by its own launch
@@ -368,8 +368,9 @@ class Environment(TorchVectorizedObject):
                 # the last draw's own tensors, unmodified, pass every check of _check_action_list by
                 # construction (a list of [B, action_size] fp32 device tensors, one per agent)
                 drawn = self._drawn
-                if not (drawn is not None and type(actions) is list and len(actions) == len(drawn[0])
-                        and all(a is t and a._version == v for a, t, v in zip(actions, drawn[0], drawn[2]))):
+                if not (drawn is not None and type(actions) is list and len(actions) == len(drawn.actions)
+                        and all(a is t and a._version == v
+                                for a, t, v in zip(actions, drawn.actions, drawn.versions))):
                     actions = self._check_action_list(actions)
                 g.before_actions()
                 if g.graph is not None:
@@ -381,7 +382,7 @@ class Environment(TorchVectorizedObject):
                         # the replay is launched before the action flags are known; a failed flag
                         # rolls the step back (StepGraph.replay_speculative) and the eager check
                         # below raises the reference's AssertionError
-                        g.backup(self._u_persist[1])
+                        g.backup(self._u_persist.buffer)
                         if self._take_preapplied(actions):  # drawn + applied by get_random_actions
                             out = g.replay_speculative(lambda: True)
                             if out is not None:
@@ -427,13 +428,12 @@ class Environment(TorchVectorizedObject):
             if apply(actions, persistent=True):
                 return self._graph.step()
             g, c = self._graph, self._apply_cache
-            if g.graph is None and g.status == "warming" and c is not None and c[1] is None:
+            if g.graph is None and g.status == "warming" and c is not None and c.refusal is not None:
                 # (the world's own configuration -- communication actions of non-silent agents, or a
                 # discrete action space the kernel does not cover -- keeps the actions on the
                 # per-agent path: every step runs eagerly; report it)
                 g.status = "eager"
-                g.why = (c[2] if len(c) > 2 else
-                         "communication actions (dim_c > 0, non-silent agents) take the per-agent action path")
+                g.why = c.refusal
         return self._step_eager(actions)
 
     def _check_action_list(self, actions):
@@ -634,25 +634,23 @@ class Environment(TorchVectorizedObject):
         if not agents:
             return None
         c = self._uniform_cache
-        if c is not None and c[1] is not None and self._uniform_same(c[2]):
+        if c is not None and c.plan is not None and self._uniform_same(c.sig):
             sp, self._spec = self._spec, None
-            if sp is not None and sp[0] is c[1]:
+            if sp is not None and sp.plan is c.plan:
                 outs = self._take_spec(sp)
                 if outs is not None:
                     return outs
-            return self._uniform_draw(c[1])
+            return self._uniform_draw(c.plan)
         plans = [self._column_plan(a) for a in agents]
         B, dev = plans[0][0], plans[0][1]
-        if c is None or len(c[0]) != len(plans) or any(a is not b for a, b in zip(c[0], plans)):
+        if c is None or len(c.key) != len(plans) or any(a is not b for a, b in zip(c.key, plans)):
             key = tuple(plans)
             n_cols = sum(p[2] for p in plans)
             ok = (n_cols <= 32 and all(p[0] == B and p[1] == dev for p in plans)
                   and self._column_draws(dev) and _uniform.mode(torch.device(dev), B) is not None)
             if not ok:
-                self._uniform_cache = (key, None)
+                self._uniform_cache = _uniform.DrawCache(key, None)
                 return None
-            from ... import _native as N
-
             cols = np.zeros(n_cols, dtype=N.UNIFORM_COLUMN_DTYPE)
             k = 0
             for p in plans:
@@ -665,13 +663,14 @@ class Environment(TorchVectorizedObject):
             # column k's byte offset in the [A, B, n] allocation of equal widths
             offs = (np.array([a * 4 * B * widths[0] + 4 * j for a in range(len(widths)) for j in range(widths[0])],
                              dtype=np.uint64) if len(set(widths)) == 1 else None)
-            c = (key, (N, cols, widths, idx, _uniform.mode(d, B), torch.cuda.default_generators[idx],
-                       cols.ctypes.data, B, dev, offs))
-        if c[1] is None:
+            c = _uniform.DrawCache(key, _uniform.ColumnDrawPlan(
+                N, cols, widths, idx, _uniform.mode(d, B), torch.cuda.default_generators[idx], cols.ctypes.data, B,
+                dev, offs))
+        if c.plan is None:
             self._uniform_cache = c
             return None
-        self._uniform_cache = (c[0], c[1], self._uniform_sig())
-        return self._uniform_draw(c[1])
+        self._uniform_cache = c._replace(sig=self._uniform_sig())
+        return self._uniform_draw(c.plan)
 
     # ---- random actions drawn ahead, inside the post-replay launch (graph mode) ------------------
     # In the loop env.step(env.get_random_actions()) the draw of step t + 1 is the next device work
@@ -689,36 +688,40 @@ class Environment(TorchVectorizedObject):
         if not (self._SPEC_DRAW and self._spec_ok) or self._ushadow.active:
             return None
         c = self._uniform_cache
-        if c is None or c[1] is None or len(c) < 3 or not self._uniform_same(c[2]):
+        if c is None or c.plan is None or not self._uniform_same(c.sig):
             return None
-        st = c[1]
-        if st[9] is None or len(st[1]) > 16:  # (equal widths; at most 16 columns in the merged launch)
+        st = c.plan
+        if st.offsets is None or len(st.cols) > 16:  # (equal widths; at most 16 columns in the merged launch)
             return None
-        N = st[0]
+        drawer = self._uniform_drawer(st)
+        if not self._preapply_columns(st):
+            return None
+        return st, drawer, self._u_persist.buffer
+
+    def _uniform_drawer(self, st):
+        # (equal widths: one [A, B, n] allocation, the table, the launch and the generator advance in one C++ call)
         h = self._uniform_host
         if h is None or h[0] is not st:
             h = self._uniform_host = (st, N.load_host().UniformDraw(
-                st[3], st[7], len(st[2]), st[2][0], st[1], st[6], len(st[1]), [int(o) for o in st[9]], st[4],
-                N.fn_addr("vmas_uniform_columns_snap"), N.fn_addr("vmas_aux_last_error")))
-        if not self._preapply_columns(st):
-            return None
-        return st, h[1], self._u_persist[1]
+                st.idx, st.B, len(st.widths), st.widths[0], st.cols, st.cols_addr, len(st.cols),
+                [int(o) for o in st.offsets], st.mode, N.fn_addr("vmas_uniform_columns_snap"),
+                N.fn_addr("vmas_aux_last_error")))
+        return h[1]
 
     def _drew_ahead(self, st, acts, snap, seed, offset, inc) -> None:
-        self._ushadow.arm(self._u_persist[1], snap)
-        self._spec = (st, acts, seed, offset, inc, self._preapply_tag)
+        self._ushadow.arm(self._u_persist.buffer, snap)
+        self._spec = _uniform.SpecDraw(st, acts, seed, offset, inc, self._preapply_tag)
 
     def _take_spec(self, sp):
         """The draw made ahead, if it is what a draw now would give: the same generator state, the
         same column plan and applied-column fields."""
-        st, acts, seed, offset, inc, tag = sp
-        gen = st[5]
-        if gen.initial_seed() != seed or gen.get_offset() != offset or not self._preapply_columns(st) \
-                or self._preapply_tag is not tag:
+        st, acts = sp.plan, sp.actions
+        gen = st.gen
+        if gen.initial_seed() != sp.seed or gen.get_offset() != sp.offset or not self._preapply_columns(st) \
+                or self._preapply_tag is not sp.tag:
             return None
-        gen.set_offset(offset + inc)
-        self._drawn = (tuple(acts), tuple(o.data_ptr() for o in acts), tuple(o._version for o in acts),
-                       self._u_persist[1])
+        gen.set_offset(sp.offset + sp.inc)
+        self._drawn = _uniform.drawn(acts, self._u_persist.buffer)
         self.drawn_ahead = getattr(self, "drawn_ahead", 0) + 1
         return acts
 
@@ -730,16 +733,15 @@ class Environment(TorchVectorizedObject):
         given exactly these tensors, unmodified, then needs no action launch: uniform draws from
         [-u_range, u_range] pass the NaN / range checks by construction (environment.py:621-655).
         Sets (or clears) the columns' second outputs; returns whether they are set."""
-        cols = st[1]
+        cols = st.cols
         g = self._graph
         ok = (g is not None and g.graph is not None and self._can_speculate())
         if ok:
-            c = self._apply_cache
-            refs, sizes = c[1][0], c[1][4]
-            widths = st[2]
-            ok = list(widths) == list(sizes)
+            plan = self._apply_cache
+            refs, sizes = plan.refs, plan.sizes
+            ok = list(st.widths) == list(sizes)
         if ok:
-            key = (id(c), self._u_persist[1].data_ptr())
+            key = (id(plan), self._u_persist.buffer.data_ptr())
             pre = self._preapply
             if pre is None or pre[0] != key:
                 pre = None
@@ -748,7 +750,7 @@ class Environment(TorchVectorizedObject):
                     r = ag.action.u_range_tensor.detach().cpu().tolist()
                     m = ag.action.u_multiplier_tensor.detach().cpu().tolist()
                     vals.append((r, m))
-                base = self._u_persist[1].data_ptr()
+                base = self._u_persist.buffer.data_ptr()
                 u_out, u_rng, u_mul = [], [], []
                 k = 0
                 good = True
@@ -787,13 +789,13 @@ class Environment(TorchVectorizedObject):
         speculative path's state after its action launch) and return True."""
         d = self._drawn
         self._drawn = None
-        if (d is None or len(actions) != len(d[0]) or self._u_persist is None or d[3] is not self._u_persist[1]
-                or getattr(self._graph, "copied", True)):
+        if (d is None or len(actions) != len(d.actions) or self._u_persist is None
+                or d.buffer is not self._u_persist.buffer or getattr(self._graph, "copied", True)):
             return False
-        for a, t, ptr, ver in zip(actions, d[0], d[1], d[2]):
+        for a, t, ptr, ver in zip(actions, d.actions, d.ptrs, d.versions):
             if a is not t or a.data_ptr() != ptr or a._version != ver:
                 return False
-        us = self._u_persist[2]
+        us = self._u_persist.views
         if us is None:
             return False
         for i, ag in enumerate(self.agents):
@@ -845,15 +847,8 @@ class Environment(TorchVectorizedObject):
         return True
 
     def _uniform_draw(self, st):
-        N, cols, widths, idx, mode, gen, cols_addr, B, dev, offs = st
-        if offs is not None:
-            # equal widths: one [A, B, n] allocation, the column table, the launch and the
-            # generator advance in one C++ call (csrc/vmas_host.cpp UniformDraw)
-            h = self._uniform_host
-            if h is None or h[0] is not st:
-                h = self._uniform_host = (st, N.load_host().UniformDraw(
-                    idx, B, len(widths), widths[0], cols, cols_addr, len(cols), [int(o) for o in offs], mode,
-                    N.fn_addr("vmas_uniform_columns_snap"), N.fn_addr("vmas_aux_last_error")))
+        if st.offsets is not None:
+            drawer = self._uniform_drawer(st)  # (equal widths: the whole draw in one C++ call)
             pre = self._preapply_columns(st)
             sh = self._ushadow
             if pre and not sh.active:
@@ -861,33 +856,26 @@ class Environment(TorchVectorizedObject):
                 # holonomic agent's state.force) view until the step consumes the draw: their
                 # current values go to a snapshot first, which those attributes show meanwhile
                 # (the reference's draw has no side effect on the agents, environment.py:524-582)
-                P = self._u_persist[1]
-                outs, snap = h[1].draw(P.data_ptr(), P.numel())
+                P = self._u_persist.buffer
+                outs, snap = drawer.draw(P.data_ptr(), P.numel())
                 sh.arm(P, snap)
             else:
-                outs, _ = h[1].draw(0, 0)
-            self._drawn = (tuple(outs), tuple(o.data_ptr() for o in outs), tuple(o._version for o in outs),
-                           self._u_persist[1]) if pre else None
+                outs, _ = drawer.draw(0, 0)
+            self._drawn = _uniform.drawn(outs, self._u_persist.buffer) if pre else None
             return outs
-        f_out = cols["out"]
-        if offs is not None:  # one allocation, one [B, n] view per agent (disjoint rows)
-            buf = torch.empty(len(widths), B, widths[0], device=dev, dtype=torch.float32)
-            outs = list(buf.unbind(0))
-            np.add(offs, buf.data_ptr(), out=f_out, casting="unsafe")
-        else:
-            outs = []
-            k = 0
-            for n in widths:
-                out = torch.empty(B, n, device=dev, dtype=torch.float32)
-                base = out.data_ptr()
-                for j in range(n):
-                    f_out[k] = base + 4 * j
-                    k += 1
-                outs.append(out)
+        f_out = st.cols["out"]  # (unequal widths: one [B, n] tensor per agent)
+        outs = []
+        k = 0
+        for n in st.widths:
+            out = torch.empty(st.B, n, device=st.dev, dtype=torch.float32)
+            base = out.data_ptr()
+            for j in range(n):
+                f_out[k] = base + 4 * j
+                k += 1
+            outs.append(out)
         pre = self._preapply_columns(st)
-        _uniform.launch(idx, B, cols, mode, gen, cols_addr)
-        self._drawn = (tuple(outs), tuple(o.data_ptr() for o in outs), tuple(o._version for o in outs),
-                       self._u_persist[1]) if pre else None
+        _uniform.launch(st.idx, st.B, st.cols, st.mode, st.gen, st.cols_addr)
+        self._drawn = _uniform.drawn(outs, self._u_persist.buffer) if pre else None
         return outs
 
     @local_seed(vmas_random_state)
@@ -938,8 +926,6 @@ class Environment(TorchVectorizedObject):
         fp32 actions (the normal case) are checked by one native kernel (vmas_check_actions);
         other dtypes keep the reference's torch comparisons in their own dtype."""
         if all(a.dtype == torch.float32 for a in actions):
-            from ... import _native as N
-
             n = len(actions)
             refs = np.zeros(n, dtype=N.ACTION_REF_DTYPE)
             keep = []
@@ -952,12 +938,7 @@ class Environment(TorchVectorizedObject):
                 refs[i] = (a.data_ptr(), r.data_ptr(), a.stride(0), a.stride(1), a.shape[1],
                            agent.action_size, int(bool(self.clamp_action)), 0)
             flags = np.zeros(2 * max(n, 1), dtype=np.uint8)
-            dev = self.device
-            if dev.type == "cuda":
-                idx = dev.index if dev.index is not None else torch.cuda.current_device()
-                stream = ctypes.c_void_p(torch.cuda.current_stream(idx).cuda_stream)
-            else:
-                idx, stream = -1, None
+            idx, stream = N.launch_args(self.device)
             N.check(N.load_library().vmas_check_actions(idx, self.num_envs, refs.ctypes.data, n,
                                                         flags.ctypes.data, stream), "vmas_check_actions")
             del keep
@@ -996,279 +977,15 @@ class Environment(TorchVectorizedObject):
         return "" if self._graph is None else getattr(self._graph, "why", "")
 
     def _apply_continuous_actions(self, actions, persistent: bool = False, speculative: bool = False):
-        """_set_action of every agent in one native call (vmas_apply_actions), for continuous fp32
-        actions without communication and without autograd: the NaN / range checks, the clamp
-        and u = physical * u_multiplier of environment.py:615-709, one launch and no stream
-        synchronisation.  Agents are then processed in order exactly as the reference loop does
-        (agent i raises before its u is assigned; the agents before it keep their new u and
-        noise).  Returns False when the case does not apply (the per-agent path runs).
-
-        speculative (graph mode, no action noise, at most 8 agents): the kernel is only launched
-        and the agents' u are bound to the persistent buffer; returns the launch's sequence number
-        (or False) and the caller checks the flags later with _finish_speculative_actions."""
-        agents = self.agents
-        n = len(agents)
-        # the persistent buffer is rewritten: a draw's applied values are stale, and so is a draw
-        # made ahead into it (_take_spec would hand out actions whose applied values are gone)
-        self._drawn = None
-        self._spec = None
-        self._ushadow.disarm()
-        if n == 0:
-            return False
-        for a in actions:
-            if a.dtype is not torch.float32 or (self.grad_enabled and a.requires_grad):
-                return False
-        dev = self.device
-        B = self.num_envs
-        c = self._apply_cache
-        key = (tuple(agents), bool(self.clamp_action), B, self.world.dim_c, str(dev))
-        if c is None or c[0] != key:
-            if self.world.dim_c > 0 and any(not ag.silent for ag in agents):
-                self._apply_cache = (key, None)
-                return False
-            from ... import _native as N
-
-            refs = np.zeros(n, dtype=N.ACTION_APPLY_REF_DTYPE)
-            sizes = [ag.action_size for ag in agents]
-            offs = np.cumsum([0] + sizes[:-1]) * B
-            tensors = []
-            for i, ag in enumerate(agents):
-                r, m = ag.action.u_range_tensor, ag.action.u_multiplier_tensor
-                if r.dtype is not torch.float32 or m.dtype is not torch.float32:
-                    self._apply_cache = (key, None)
-                    return False
-                tensors.append((r, m))
-                refs[i]["u_range"], refs[i]["u_mult"] = r.data_ptr(), m.data_ptr()
-                refs[i]["out_offset"], refs[i]["n_phys"] = int(offs[i]), sizes[i]
-                refs[i]["clamp"] = int(bool(self.clamp_action))
-            if dev.type == "cuda":
-                idx = dev.index if dev.index is not None else torch.cuda.current_device()
-            else:
-                idx = -1
-            fields = (refs["u"], refs["s0"], refs["s1"], refs["n_cols"])
-            flags = np.zeros(max(16, (2 * n + 7) // 8 * 8), dtype=np.uint8)  # (whole uint64 words)
-            # the arrays' addresses once (ndarray.ctypes builds a helper object per access: ~1.6 us)
-            c = self._apply_cache = (key, (refs, fields, flags, tensors, sizes, sum(sizes), idx, N,
-                                           refs.ctypes.data, flags.ctypes.data, flags.view(np.uint64)))
-        st = c[1]
-        if st is None:
-            return False
-        refs, (f_u, f_s0, f_s1, f_nc), flags, tensors, sizes, total, idx, N, refs_addr, flags_addr, _ = st
-        for i, ag in enumerate(agents):  # range / multiplier tensors are cached by the Action
-            if ag.action._u_range_tensor is not tensors[i][0] or ag.action._u_multiplier_tensor is not tensors[i][1]:
-                self._apply_cache = None
-                return self._apply_continuous_actions(actions, persistent, speculative)
-        if speculative and (idx < 0 or n > 8 or any(ag.action.u_noise > 0 for ag in agents)):
-            return False
-        keep = []
-        for i, a in enumerate(actions):
-            if a.device != dev:
-                a = a.to(dev)
-            keep.append(a)
-            s = a.stride()
-            f_u[i], f_s0[i], f_s1[i], f_nc[i] = a.data_ptr(), s[0], s[1], a.shape[1]
-        if persistent:  # graph mode: every step writes the same buffer / the same u views
-            pc = self._u_persist
-            if pc is None or pc[0] is not c:
-                if self._graph is not None and self._graph.graph is not None:
-                    # the captured step reads the previous buffer's views
-                    self._graph.drop("action parameters changed")
-                    if speculative:
-                        return False
-                pc = self._u_persist = (c, torch.empty(B * total, device=dev, dtype=torch.float32), None)
-            out = pc[1]
-        else:
-            out = torch.empty(B * total, device=dev, dtype=torch.float32)
-        stream = N.stream_ptr(idx) if idx >= 0 else None
-        lib = N.load_library()
-        if speculative:
-            seq = ctypes.c_uint32(0)
-            N.check_aux(lib.vmas_apply_actions_launch(idx, B, refs_addr, n, out.data_ptr(), ctypes.byref(seq), stream),
-                        "vmas_apply_actions_launch")
-            self._spec_keep = keep  # the kernel reads them: alive until the flags are in
-        else:
-            N.check_aux(lib.vmas_apply_actions(idx, B, refs_addr, n, out.data_ptr(), flags_addr, stream),
-                        "vmas_apply_actions")
-        del keep
-        k = sizes[0]
-        if persistent and self._u_persist[2] is not None:
-            us = self._u_persist[2]
-        elif all(sz == k for sz in sizes):
-            us = out.view(n, B, k).unbind(0)
-        else:
-            us = [out.narrow(0, int(o), B * sz).view(B, sz) for o, sz in zip(refs["out_offset"], sizes)]
-        if persistent and self._u_persist[2] is None:
-            self._u_persist = (self._u_persist[0], out, us)
-        if speculative:
-            for i, ag in enumerate(agents):
-                ag.action.u = us[i]
-            return seq.value
-        for i, ag in enumerate(agents):
-            if flags[2 * i]:
-                print()  # the reference prints an empty line before this assert (environment.py:621-622)
-                assert not flags[2 * i]
-            assert not flags[2 * i + 1], (
-                f"Physical actions of agent {ag.name} are out of its range {ag.u_range}"
-            )
-            ag.action.u = us[i]
-            if ag.action.u_noise > 0:
-                noise = torch.randn(*ag.action.u.shape, device=self.device, dtype=torch.float32) * ag.u_noise
-                ag.action.u += noise
-        return True
-
-    def _discrete_plan_refusal(self, multi: bool, nvecs) -> Optional[str]:
-        """Why this env's discrete actions keep the per-agent path (None: the fused path applies)."""
-        from ... import _native as N
-
-        if self.world.dim_c > 0 and any(not ag.silent for ag in self.agents):
-            return "communication actions (dim_c > 0, non-silent agents) take the per-agent action path"
-        K = N.DISCRETE_MAX_COMPONENTS
-        for ag, nvec in zip(self.agents, nvecs):
-            if not 1 <= len(nvec) <= K or ag.action_size > K:
-                return f"more than {K} discrete action components take the per-agent action path"
-            if len(nvec) > ag.action_size or (multi and len(nvec) != ag.action_size):
-                return "discrete_action_nvec does not match action_size"
-            if (not all(isinstance(n, (int, np.integer)) and 2 <= n <= 1 << 24 for n in nvec)
-                    or (not multi and math.prod(nvec) > 1 << 24)):
-                return "discrete_action_nvec beyond what fp32 holds exactly"
-            if (ag.action.u_range_tensor.dtype is not torch.float32
-                    or ag.action.u_multiplier_tensor.dtype is not torch.float32):
-                return "u_range / u_multiplier are not float32"
-        if _discrete.mode(self.device) is None:
-            return "no division mode of the discrete action kernel reproduces this torch build"
-        return None
+        """_set_action of every agent in one native call for continuous fp32 actions (_actions.apply
+        with _actions.Continuous).  Returns False when the case does not apply (the per-agent path
+        runs), True once every agent's u is set, or -- speculative -- the launch's sequence number."""
+        return _actions.apply(self, _actions.Continuous, actions, persistent, speculative)
 
     def _apply_discrete_actions(self, actions, persistent: bool = False, speculative: bool = False):
-        """_set_action of every agent in one native call (vmas_apply_discrete_actions), for
-        discrete actions (flat index or multi-discrete; int64, int32 or float32) without
-        communication and without autograd: the flat decode, the range checks, the odd-n swap and
-        u = ((a / (n - 1)) * 2 u_max - u_max) * u_multiplier of environment.py:667-709, one launch
-        and no stream synchronisation, into the buffer layout of _apply_continuous_actions (graph
-        mode's persistent buffer included).  Returns False when the case does not apply (the
-        per-agent path runs).
-
-        A set flag -- a NaN, a value out of range, a float32 flat index that is not a whole
-        number -- hands the step to the per-agent path: it raises where the reference raises (the
-        agents before the failing one keep their new u, the failing one's u is what the reference
-        leaves) or, for values the reference accepts, computes u with the reference's own float
-        arithmetic.
-
-        speculative: as _apply_continuous_actions (launch only; returns the sequence number)."""
-        agents = self.agents
-        n = len(agents)
-        self._drawn = None
-        self._spec = None
-        self._ushadow.disarm()
-        if n == 0:
-            return False
-        codes = _discrete.DTYPE_CODES
-        for a in actions:
-            if a.dtype not in codes or (self.grad_enabled and a.requires_grad):
-                return False
-        dev = self.device
-        B = self.num_envs
-        multi = bool(self.multidiscrete_actions)
-        # (nvec is a plain list the caller may re-assign or edit: compared by value every call)
-        nvecs = tuple(tuple(ag.discrete_action_nvec) for ag in agents)
-        c = self._apply_cache
-        key = ("discrete", tuple(agents), multi, nvecs, B, self.world.dim_c, str(dev))
-        if c is None or c[0] != key:
-            why = self._discrete_plan_refusal(multi, nvecs)
-            if why is not None:
-                self._apply_cache = (key, None, why)
-                return False
-            from ... import _native as N
-
-            refs = np.zeros(n, dtype=N.DISCRETE_ACTION_REF_DTYPE)
-            sizes = [ag.action_size for ag in agents]
-            offs = np.cumsum([0] + sizes[:-1]) * B
-            tensors = []
-            for i, ag in enumerate(agents):
-                r, m = ag.action.u_range_tensor, ag.action.u_multiplier_tensor
-                tensors.append((r, m))
-                refs[i]["u_range"], refs[i]["u_mult"] = r.data_ptr(), m.data_ptr()
-                refs[i]["out_offset"], refs[i]["n_phys"] = int(offs[i]), sizes[i]
-                refs[i]["flat"], refs[i]["n_comp"] = int(not multi), len(nvecs[i])
-                refs["nvec"][i, : len(nvecs[i])] = nvecs[i]
-            idx = _discrete.launch_args(dev)[0]
-            fields = (refs["a"], refs["s0"], refs["s1"], refs["dtype"])
-            flags = np.zeros(max(16, (2 * n + 7) // 8 * 8), dtype=np.uint8)  # (whole uint64 words)
-            # (the first eleven entries as _apply_continuous_actions lays them out: _can_speculate and
-            # _speculative_flags_ok read them)
-            c = self._apply_cache = (key, (refs, fields, flags, tensors, sizes, sum(sizes), idx, N,
-                                           refs.ctypes.data, flags.ctypes.data, flags.view(np.uint64),
-                                           _discrete.mode(dev)))
-        st = c[1]
-        if st is None:
-            return False
-        refs, (f_a, f_s0, f_s1, f_dt), flags, tensors, sizes, total, idx, N, refs_addr, flags_addr, _, mode = st
-        for i, ag in enumerate(agents):  # range / multiplier tensors are cached by the Action
-            if ag.action._u_range_tensor is not tensors[i][0] or ag.action._u_multiplier_tensor is not tensors[i][1]:
-                self._apply_cache = None
-                return self._apply_discrete_actions(actions, persistent, speculative)
-        if speculative and (idx < 0 or n > 8 or any(ag.action.u_noise > 0 for ag in agents)):
-            return False
-        keep = []
-        for i, a in enumerate(actions):
-            if a.device != dev:
-                a = a.to(dev)
-            if a.dim() != 2 or a.shape[0] != B or a.shape[1] != (sizes[i] if multi else 1):
-                return False  # (the per-agent path raises the reference's shape assertion)
-            keep.append(a)
-            s = a.stride()
-            f_a[i], f_s0[i], f_s1[i], f_dt[i] = a.data_ptr(), s[0], s[1], codes[a.dtype]
-        if persistent:  # graph mode: every step writes the same buffer / the same u views
-            pc = self._u_persist
-            if pc is None or pc[0] is not c:
-                if self._graph is not None and self._graph.graph is not None:
-                    # the captured step reads the previous buffer's views
-                    self._graph.drop("action parameters changed")
-                    if speculative:
-                        return False
-                pc = self._u_persist = (c, torch.empty(B * total, device=dev, dtype=torch.float32), None)
-            out = pc[1]
-        else:
-            out = torch.empty(B * total, device=dev, dtype=torch.float32)
-        stream = N.stream_ptr(idx) if idx >= 0 else None
-        lib = N.load_library()
-        if speculative:
-            seq = ctypes.c_uint32(0)
-            N.check_aux(lib.vmas_apply_discrete_actions_launch(idx, B, refs_addr, n, out.data_ptr(), mode,
-                                                               ctypes.byref(seq), stream),
-                        "vmas_apply_discrete_actions_launch")
-            self._spec_keep = keep  # the kernel reads them: alive until the flags are in
-        else:
-            N.check_aux(lib.vmas_apply_discrete_actions(idx, B, refs_addr, n, out.data_ptr(), mode, flags_addr, stream),
-                        "vmas_apply_discrete_actions")
-        del keep
-        k = sizes[0]
-        if persistent and self._u_persist[2] is not None:
-            us = self._u_persist[2]
-        elif all(sz == k for sz in sizes):
-            us = out.view(n, B, k).unbind(0)
-        else:
-            us = [out.narrow(0, int(o), B * sz).view(B, sz) for o, sz in zip(refs["out_offset"], sizes)]
-        if persistent and self._u_persist[2] is None:
-            self._u_persist = (self._u_persist[0], out, us)
-        if speculative:
-            for i, ag in enumerate(agents):
-                ag.action.u = us[i]
-            return seq.value
-        if flags[: 2 * n].any():
-            # the reference's own loop decides: it raises at the failing agent, or accepts the values
-            for i, ag in enumerate(agents):
-                self._set_action(actions[i], ag)
-            if persistent:  # (the captured step reads the persistent views)
-                for i, ag in enumerate(agents):
-                    us[i].copy_(ag.action.u)
-                    ag.action.u = us[i]
-            return True
-        for i, ag in enumerate(agents):
-            ag.action.u = us[i]
-            if ag.action.u_noise > 0:
-                noise = torch.randn(*ag.action.u.shape, device=self.device, dtype=torch.float32) * ag.u_noise
-                ag.action.u += noise
-        return True
+        """As _apply_continuous_actions, for flat-index or multi-discrete actions (_actions.Discrete),
+        into the same buffer layout (graph mode's persistent buffer included)."""
+        return _actions.apply(self, _actions.Discrete, actions, persistent, speculative)
 
     # Speculative replay (default; VMAS_GRAPH_SPECULATIVE=0 turns it off): launch the replay
     # before the action flags are known and roll the step back on a failed flag.  Interleaved
@@ -1278,9 +995,9 @@ class Environment(TorchVectorizedObject):
     _SPECULATE = os.environ.get("VMAS_GRAPH_SPECULATIVE", "1") != "0"
 
     def _can_speculate(self) -> bool:
-        c = self._apply_cache
-        if not (self._SPECULATE and c is not None and c[1] is not None and c[1][6] >= 0 and len(self.agents) <= 8
-                and self._u_persist is not None and self._u_persist[0] is c):
+        plan = self._apply_cache
+        if not (self._SPECULATE and plan is not None and plan.refusal is None and plan.idx >= 0
+                and len(self.agents) <= 8 and self._u_persist is not None and self._u_persist.plan is plan):
             return False
         for ag in self.agents:  # (the Action's own field: u_noise is a property per call)
             if ag._action._u_noise > 0:
@@ -1289,10 +1006,10 @@ class Environment(TorchVectorizedObject):
 
     def _speculative_flags_ok(self, seq: int) -> bool:
         """Waits for the flags of a speculative launch; True when every agent's actions pass."""
-        st = self._apply_cache[1]
-        idx, N, flags_addr, words = st[6], st[7], st[9], st[10]
-        N.check_aux(N.load_library().vmas_apply_actions_flags(idx, seq, len(self.agents), flags_addr, N.stream_ptr(idx)),
-                    "vmas_apply_actions_flags")
+        plan = self._apply_cache
+        idx, words = plan.idx, plan.words
+        N.check_aux(N.load_library().vmas_apply_actions_flags(idx, seq, len(self.agents), plan.flags_addr,
+                                                              N.stream_ptr(idx)), "vmas_apply_actions_flags")
         self._spec_keep = None
         return not (int(words[0]) | int(words[1]))  # (speculation: at most 8 agents, 16 flag bytes)
 
