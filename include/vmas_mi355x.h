@@ -44,8 +44,10 @@ extern "C" {
  * v4: VmasSpawnTargetsIO max_tries / backup; vmas_uniform_columns_snap
  * v5: VmasSpawnTargetsIO scratch / scratch_words (the windowed respawn), vmas_spawn_scratch_words;
  *     the fused programs' out_delta (direct outputs) and VMAS_COPY_STORE64 spans
- * v7: VmasDiscreteActionRef, vmas_apply_discrete_actions / _launch */
-#define VMAS_ABI_VERSION 7
+ * v7: VmasDiscreteActionRef, vmas_apply_discrete_actions / _launch
+ * v8: VmasRenderPrim / VmasRenderEntity / VmasRenderLidar / VmasRenderScene, vmas_render_frames,
+ *     vmas_render_scene */
+#define VMAS_ABI_VERSION 8
 
 /* error codes */
 #define VMAS_OK 0
@@ -902,6 +904,117 @@ const char* vmas_jit_last_error(void);
  * (at most 32, VMAS_JIT_CACHE overrides).  Test / diagnostics entry point, no reference
  * counterpart. */
 int32_t vmas_jit_stats(int64_t* compiles, int64_t* cached);
+
+/* ------------------------------------------------------------------------------------------------
+ * rgb_array rendering (csrc/vmas_render.hip; no reference counterpart: the reference draws through
+ * pyglet / OpenGL, vmas/simulator/rendering.py).  A frame is H x W x 3 uint8, row 0 at the top.
+ * Primitives live in PIXEL space: x = (wx - left) * W / (right - left), y = (wy - bottom) * H /
+ * (top - bottom), y up; the centre of pixel (i, j) is (j + 0.5, H - i - 0.5).  Every primitive has a
+ * signed distance d (pixels, negative inside) from the pixel centre:
+ *   DISC  p = cx, cy, r            d = |q - c| - r
+ *   POLY  v0, nv (>= 3) into verts d = least distance to an edge, negative inside (even-odd rule)
+ *   SEG   p = ax, ay, bx, by, w    d = dist(q, ab) - w/2           (round ends)
+ *   RING  p = cx, cy, r, w         d = ||q - c| - r| - w/2
+ *   GRID  p = ox, oy, spacing, half, w, c0; v0 = m_lo, nv = m_hi
+ *         lines at -half + k * spacing (k = 0..n-1) from (ox, oy) in x and in y, inside the square
+ *         |q - o| <= half per axis: d = distance to the nearest line - w/2; no coverage outside.
+ *         The record names the lines from the one nearest the origin, k0 = round(half / spacing):
+ *         c0 = k0 * spacing - half, and line m = k - k0 (m_lo = -k0 .. m_hi = n - 1 - k0) lies at
+ *         c0 + m * spacing, which keeps the fp32 arithmetic on numbers of the frame's size
+ * A line width w below 1 is drawn as 1.  Compositing is fp32 with separate roundings:
+ * cov = clamp(0.5 - d, 0, 1); out starts (1, 1, 1); each primitive in table order does
+ * out = out * (1 - a * cov) + rgb * (a * cov); a DISC / POLY with VMAS_PRIM_BORDER then draws
+ * d_b = |d| - 1 in 0.5 * rgb at 0.5 * a; the pixel is floor(255 * out + 0.5).
+ * bbox = xmin, ymin, xmax, ymax (pixel space) must hold every point with d < 0.5 (border: |d| < 1.5):
+ * the device kernel culls a primitive from the 16 x 16 tiles its bbox does not touch. */
+#define VMAS_PRIM_NONE 0 /* skipped */
+#define VMAS_PRIM_DISC 1
+#define VMAS_PRIM_POLY 2
+#define VMAS_PRIM_SEG 3
+#define VMAS_PRIM_RING 4
+#define VMAS_PRIM_GRID 5
+#define VMAS_PRIM_BORDER 1 /* flags */
+
+typedef struct VmasRenderPrim {
+    int32_t kind;  /* VMAS_PRIM_* */
+    int32_t flags; /* VMAS_PRIM_BORDER */
+    float rgba[4];
+    float p[6];
+    int32_t v0, nv; /* POLY: its vertices verts[2 * v0 .. 2 * (v0 + nv)) */
+    float bbox[4];
+} VmasRenderPrim; /* 72 bytes */
+
+/* Rasterises n_frames frames of height x width: frame e composites prims[e * n_prims .. + n_prims)
+ * in order into out[e] ([n_frames, height, width, 3] uint8).  verts: the x, y pairs POLY records
+ * index (one pool for every frame; may be NULL when n_verts == 0).  device >= 0: one launch on
+ * `stream`, one workgroup per 16 x 16 tile, no atomics; device < 0: the same arithmetic on the host. */
+int32_t vmas_render_frames(int32_t device, int32_t n_frames, int32_t height, int32_t width,
+                           const VmasRenderPrim* prims, int32_t n_prims, const float* verts,
+                           int32_t n_verts, uint8_t* out, void* stream);
+
+#define VMAS_RENDER_AGENT 1  /* VmasRenderEntity.flags: counts for the shared camera's fit */
+#define VMAS_RENDER_ACTION 2 /* draws its action line (force != NULL) */
+#define VMAS_RENDER_MAX_AGENTS 32
+
+typedef struct VmasRenderEntity {
+    const float* pos;    /* [B, 2] */
+    const float* rot;    /* [B, 1] */
+    const float* color;  /* [3] (color_s0 == 0) or [B, 3] */
+    const uint8_t* mask; /* is_rendering [B] (bool), or NULL */
+    const float* force;  /* [B, 2] of an action line, or NULL */
+    int32_t pos_s0, rot_s0, color_s0, force_s0; /* row strides in elements */
+    int32_t shape;                              /* VMAS_SPHERE / VMAS_BOX / VMAS_LINE */
+    int32_t flags;                              /* VMAS_RENDER_* */
+    float radius, length, width; /* of the shape (a line's width is its GL width in pixels) */
+    float alpha;
+    float action_scale; /* the action line ends at pos + force * action_scale */
+    int32_t slot;       /* the entity's record in an env's row of the table */
+    int32_t action_slot;
+    int32_t vert_slot;  /* BOX: its 4 vertices are verts[(e * n_boxes + vert_slot) * 4 ..] */
+} VmasRenderEntity; /* 96 bytes */
+
+typedef struct VmasRenderLidar {
+    const float* pos;    /* the agent's [B, 2] */
+    const float* rot;    /* the agent's [B, 1] */
+    const float* angles; /* [B, n_rays] (angles_s0 == 0: one shared row) */
+    const float* dist;   /* the last measurement [B, n_rays] */
+    const uint8_t* mask; /* the agent's is_rendering, or NULL */
+    int32_t pos_s0, rot_s0, angles_s0, dist_s0;
+    int32_t n_rays;
+    int32_t slot; /* ray k: SEG at slot + 2k, end DISC (world radius 0.01) at slot + 2k + 1 */
+    float alpha;
+    float rgb[3]; /* the end discs' colour (the rays are black) */
+} VmasRenderLidar; /* 80 bytes */
+
+typedef struct VmasRenderScene {
+    int32_t width, height;   /* of a frame */
+    int32_t focus;           /* index into the entity list of the agent the camera follows, or -1 */
+    int32_t n_boundary;      /* boundary segments (slots 0 .. n_boundary - 1): 0..4 */
+    float boundary[4][4];    /* ax, ay, bx, by in world units (GRAY, GL width 0.7) */
+    int32_t plot_grid;       /* 1: a GRID record at slot n_boundary (0.15 grey, alpha 0.3) */
+    float grid_spacing;
+    float origin[2];         /* scenario.render_origin */
+    float zoom;              /* scenario.viewer_zoom (> 0) */
+    float max_agent_radius;  /* largest circumscribed radius of the agents */
+    int32_t n_boxes;         /* BOX entities (vertex pool rows per env) */
+    int32_t n_prims;         /* records per env: every slot is written by every call */
+    int32_t batch;           /* B: an index outside 0..B-1 is clamped into it */
+} VmasRenderScene;
+
+/* Builds, for the n_frames environments env_index[0..n_frames) (NULL: 0..n_frames-1) of a batch,
+ * the camera bounds (reference environment.py:851-903, the plain affine map) and the entity layer
+ * of the primitive table: boundary, grid, each entity's shape (a sphere a bordered DISC, a box a
+ * bordered POLY, a line a SEG), per LIDAR ray a SEG and an end DISC, and the action lines, at the
+ * slots the descriptors name.  prims [n_frames, scene->n_prims], verts [n_frames, n_boxes, 4, 2]
+ * and bounds [n_frames, 4] (left, right, bottom, top) are outputs.  entities / lidars / scene are
+ * host arrays (copied into the launch); every other pointer is a device pointer when device >= 0
+ * (one thread per environment and entity or ray, stream-ordered, nothing waits) and a host pointer
+ * when device < 0.  At most VMAS_RENDER_MAX_AGENTS entities may carry VMAS_RENDER_AGENT. */
+int32_t vmas_render_scene(int32_t device, int32_t n_frames, const int64_t* env_index,
+                          const VmasRenderEntity* entities, int32_t n_entities,
+                          const VmasRenderLidar* lidars, int32_t n_lidars,
+                          const VmasRenderScene* scene, VmasRenderPrim* prims, float* verts,
+                          float* bounds, void* stream);
 
 #ifdef __cplusplus
 }

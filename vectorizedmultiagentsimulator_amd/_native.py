@@ -19,7 +19,7 @@ LIB_PATH = Path(os.environ.get("VMAS_LIB_PATH") or Path(__file__).resolve().pare
 
 # ------------------------------------------------------------------------------------------------
 # constants mirrored from include/vmas_mi355x.h
-VMAS_ABI_VERSION = 7
+VMAS_ABI_VERSION = 8
 VMAS_SPHERE, VMAS_BOX, VMAS_LINE = 0, 1, 2
 (
     VMAS_PAIR_JOINT,
@@ -125,6 +125,8 @@ EXPORTED_SYMBOLS = (
     "vmas_jit_world_set_params",
     "vmas_jit_stats",
     "vmas_jit_last_error",
+    "vmas_render_frames",
+    "vmas_render_scene",
 )
 
 _i32 = ctypes.c_int32
@@ -348,6 +350,38 @@ def copy_spans(device_index: int, pairs, stream) -> None:
     """dst.copy_(src) for every (dst, src) pair of same-size contiguous device tensors, all in one
     native launch (vmas_copy_spans; any dtype: bytes are copied)."""
     copy_raw(device_index, [(s.data_ptr(), d.data_ptr(), d.numel() * d.element_size()) for d, s in pairs], stream)
+
+
+# rendering (csrc/vmas_render.hip)
+VMAS_PRIM_NONE, VMAS_PRIM_DISC, VMAS_PRIM_POLY, VMAS_PRIM_SEG, VMAS_PRIM_RING, VMAS_PRIM_GRID = range(6)
+VMAS_PRIM_BORDER = 1
+VMAS_RENDER_AGENT, VMAS_RENDER_ACTION = 1, 2
+VMAS_RENDER_MAX_AGENTS = 32
+RENDER_PRIM_DTYPE = np.dtype([("kind", np.int32), ("flags", np.int32), ("rgba", np.float32, 4), ("p", np.float32, 6),
+                              ("v0", np.int32), ("nv", np.int32), ("bbox", np.float32, 4)])  # VmasRenderPrim
+assert RENDER_PRIM_DTYPE.itemsize == 72
+
+
+class VmasRenderEntity(ctypes.Structure):
+    _fields_ = [("pos", _vp), ("rot", _vp), ("color", _vp), ("mask", _vp), ("force", _vp),
+                ("pos_s0", _i32), ("rot_s0", _i32), ("color_s0", _i32), ("force_s0", _i32),
+                ("shape", _i32), ("flags", _i32), ("radius", _f32), ("length", _f32), ("width", _f32),
+                ("alpha", _f32), ("action_scale", _f32), ("slot", _i32), ("action_slot", _i32), ("vert_slot", _i32)]
+
+
+class VmasRenderLidar(ctypes.Structure):
+    _fields_ = [("pos", _vp), ("rot", _vp), ("angles", _vp), ("dist", _vp), ("mask", _vp),
+                ("pos_s0", _i32), ("rot_s0", _i32), ("angles_s0", _i32), ("dist_s0", _i32),
+                ("n_rays", _i32), ("slot", _i32), ("alpha", _f32), ("rgb", _f32 * 3)]
+
+
+class VmasRenderScene(ctypes.Structure):
+    _fields_ = [("width", _i32), ("height", _i32), ("focus", _i32), ("n_boundary", _i32),
+                ("boundary", (_f32 * 4) * 4), ("plot_grid", _i32), ("grid_spacing", _f32), ("origin", _f32 * 2),
+                ("zoom", _f32), ("max_agent_radius", _f32), ("n_boxes", _i32), ("n_prims", _i32), ("batch", _i32)]
+
+
+assert ctypes.sizeof(VmasRenderEntity) == 96 and ctypes.sizeof(VmasRenderLidar) == 80
 
 
 class VmasGradIO(ctypes.Structure):
@@ -691,6 +725,10 @@ def load_library(path: os.PathLike | str | None = None) -> ctypes.CDLL:
         ctypes.POINTER(_i32), ctypes.POINTER(_i32), _vp,
     ]
     lib.vmas_aux_last_error.restype = ctypes.c_char_p
+    lib.vmas_render_frames.restype = _i32
+    lib.vmas_render_frames.argtypes = [_i32, _i32, _i32, _i32, _vp, _i32, _vp, _i32, _vp, _vp]
+    lib.vmas_render_scene.restype = _i32
+    lib.vmas_render_scene.argtypes = [_i32, _i32, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp]
     lib.vmas_jit_world_create.restype = _i32
     lib.vmas_jit_world_create.argtypes = [_vp, _vp, _vp, _vp, ctypes.POINTER(_vp)]
     lib.vmas_jit_world_destroy.restype = _i32

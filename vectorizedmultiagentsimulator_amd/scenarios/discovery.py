@@ -450,6 +450,32 @@ class Scenario(BaseScenario):
             return c[2]
         return at.all(dim=-1)
 
+    def extra_render(self, env_index: int = 0):
+        """discovery.py:267-299: a ring of covering_range around every target, and a line between
+        each pair of agents within communication range (positions read with one copy)."""
+        from vectorizedmultiagentsimulator_amd.simulator import rendering
+
+        agents = self.world.agents
+        pos = torch.stack([e.state.pos[env_index] for e in self._targets + agents]).tolist()
+        t_pos, a_pos = pos[: len(self._targets)], pos[len(self._targets):]
+        geoms = []
+        for p in t_pos:
+            ring = rendering.make_circle(self._covering_range, filled=False)
+            xform = rendering.Transform()
+            xform.set_translation(*p)
+            ring.add_attr(xform)
+            ring.set_color(*self.target_color.value)
+            geoms.append(ring)
+        for i in range(len(agents)):
+            for j in range(i + 1, len(agents)):
+                (ax, ay), (bx, by) = a_pos[i], a_pos[j]
+                if ((ax - bx) ** 2 + (ay - by) ** 2) ** 0.5 <= self._comms_range:
+                    line = rendering.Line((ax, ay), (bx, by), width=1)
+                    line.add_attr(rendering.Transform())
+                    line.set_color(*Color.BLACK.value)
+                    geoms.append(line)
+        return geoms
+
 
 class HeuristicPolicy(BaseHeuristicPolicy):
     """Circle at r=0.75; steer towards visible targets and away from close agents."""

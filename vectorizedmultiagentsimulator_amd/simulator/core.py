@@ -110,7 +110,7 @@ class Shape(ABC):
         raise NotImplementedError
 
     def get_geometry(self):
-        raise NotImplementedError("rendering is not part of the MI355X engine")
+        raise NotImplementedError
 
 
 class Box(Shape):
@@ -144,6 +144,12 @@ class Box(Shape):
     def circumscribed_radius(self):
         return math.sqrt((self.length / 2) ** 2 + (self.width / 2) ** 2)
 
+    def get_geometry(self):
+        from . import rendering
+
+        hl, hw = self.length / 2, self.width / 2
+        return rendering.make_polygon([(-hl, -hw), (-hl, hw), (hl, hw), (hl, -hw)])
+
 
 class Sphere(Shape):
     def __init__(self, radius: float = 0.05):
@@ -169,6 +175,11 @@ class Sphere(Shape):
     def circumscribed_radius(self):
         return self.radius
 
+    def get_geometry(self):
+        from . import rendering
+
+        return rendering.make_circle(self.radius)
+
 
 class Line(Shape):
     def __init__(self, length: float = 0.5):
@@ -193,6 +204,11 @@ class Line(Shape):
 
     def get_delta_from_anchor(self, anchor):
         return anchor[X] * self.length / 2, 0.0
+
+    def get_geometry(self):
+        from . import rendering
+
+        return rendering.Line((-self.length / 2, 0), (self.length / 2, 0), width=self.width)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -707,7 +723,23 @@ class Entity(TorchVectorizedObject, Observable, ABC):
         self.state.to(device)
 
     def render(self, env_index: int = 0):
-        raise NotImplementedError("rendering is not part of the MI355X engine")
+        """The entity's geoms for one environment (core.py:767-784).  Values come from the frame's
+        host snapshot when Environment.render took one (simulator/_render.py), else from the tensors."""
+        from . import rendering
+        from ._render import host_value
+
+        if not host_value(self, "mask", env_index, lambda: self.is_rendering[env_index])[0]:
+            return []
+        geom = self.shape.get_geometry()
+        xform = rendering.Transform()
+        geom.add_attr(xform)
+        xform.set_translation(*host_value(self, "pos", env_index, lambda: self.state.pos[env_index]))
+        xform.set_rotation(host_value(self, "rot", env_index, lambda: self.state.rot[env_index])[0])
+        color = self.color
+        if isinstance(color, Tensor):
+            color = host_value(self, "color", env_index, lambda: color[env_index] if color.dim() > 1 else color)
+        geom.set_color(*color)
+        return [geom]
 
 
 class Landmark(Entity):
@@ -959,6 +991,30 @@ class Agent(Entity):
         self.action.to(device)
         for sensor in self.sensors:
             sensor.to(device)
+
+    @override(Entity)
+    def render(self, env_index: int = 0):
+        """core.py:1064-1085: the shape in the agent's alpha, its sensors, the action line."""
+        from . import rendering
+        from ._render import host_value
+
+        geoms = super().render(env_index)
+        if len(geoms) == 0:
+            return geoms
+        color = geoms[0]._color.vec4[:3]
+        for geom in geoms:
+            geom.set_color(*color, alpha=self._alpha)
+        if self._sensors is not None:
+            for sensor in self._sensors:
+                geoms += sensor.render(env_index=env_index)
+        if self._render_action and self.state.force is not None:
+            pos = host_value(self, "pos", env_index, lambda: self.state.pos[env_index])
+            force = host_value(self, "force", env_index, lambda: self.state.force[env_index])
+            scale = 10 * self.shape.circumscribed_radius()
+            line = rendering.Line((pos[0], pos[1]), (pos[0] + force[0] * scale, pos[1] + force[1] * scale), width=2)
+            line.set_color(*color)
+            geoms.append(line)
+        return geoms
 
 
 # ------------------------------------------------------------------------------------------------

@@ -8,7 +8,8 @@ SURVEY.md); results and exceptions are the same:
     step instead of two per agent (environment.py:621-623, 653-655);
   * random actions take their bounds from the python ``u_range`` values (the same fp32 numbers
     the reference reads back from ``u_range_tensor`` with a sync per call).
-Rendering is outside the scope of the MI355X engine.
+``render(mode="rgb_array")`` and ``render_batch`` draw on the native rasteriser (simulator/_render.py);
+windows and interactive rendering are outside the scope of the MI355X engine.
 """
 from __future__ import annotations
 
@@ -1103,8 +1104,53 @@ class Environment(TorchVectorizedObject):
                 noise = torch.randn(*agent.action.c.shape, device=self.device, dtype=torch.float32) * agent.c_noise
                 agent.action.c += noise
 
-    def render(self, *args, **kwargs):
-        raise NotImplementedError("rendering is not part of the MI355X engine")
+    @local_seed(vmas_random_state)
+    def render(
+        self,
+        mode="human",
+        env_index=0,
+        agent_index_focus: Optional[int] = None,
+        visualize_when_rgb: bool = False,
+        plot_position_function=None,
+        plot_position_function_precision: float = 0.01,
+        plot_position_function_range=None,
+        plot_position_function_cmap_range=None,
+        plot_position_function_cmap_alpha: Optional[float] = 1.0,
+        plot_position_function_cmap_name: Optional[str] = "viridis",
+    ):
+        """One environment's frame (the reference's signature, environment.py:757-939).
+
+        ``mode="rgb_array"`` returns a NumPy uint8 array of shape (viewer_size[1], viewer_size[0], 3)
+        drawn by the native rasteriser (simulator/_render.py, csrc/vmas_render.hip): the geoms are
+        collected as the reference collects them (boundary, grid, ``extra_render``, every entity's
+        ``render``, ``top_layer_render``), with the reference's camera, on ``cpu`` and ROCm devices
+        alike.  There is no window: ``mode="human"``, ``visualize_when_rgb=True`` and a
+        ``plot_position_function`` raise NotImplementedError; use ``mode="rgb_array"``.
+
+        :param agent_index_focus: the camera follows this agent; None: it stays on
+            ``scenario.render_origin`` and zooms out to contain all agents"""
+        from .. import _render
+
+        return _render.render_frame(self, mode, env_index, agent_index_focus, visualize_when_rgb,
+                                    plot_position_function)
+
+    def render_batch(self, env_indices=None, size=None, agent_index_focus: Optional[int] = None) -> Tensor:
+        """Frames of many environments in two native launches: a uint8 tensor [E, H, W, 3] on the
+        environment's device (no reference counterpart).
+
+        :param env_indices: a list or an integer tensor of environment indices (a tensor's values
+            are not checked on the host: one outside the batch is clamped into it); None: all
+        :param size: (W, H) of a frame; default ``scenario.viewer_size``
+        :param agent_index_focus: as in :meth:`render`
+
+        Drawn: the semidim boundary, the grid and the entity layer (shapes, LIDAR rays, action
+        lines) with :meth:`render`'s camera per environment.  ``scenario.extra_render`` and
+        ``top_layer_render`` are Python per environment and are NOT part of these frames; an entity
+        or sensor whose class overrides ``render`` raises NotImplementedError.  The launches are
+        ordered on the current stream and nothing waits on the host."""
+        from .. import _render
+
+        return _render.render_batch(self, env_indices, size, agent_index_focus)
 
     @override(TorchVectorizedObject)
     def to(self, device: DEVICE_TYPING):

@@ -15,6 +15,8 @@ import torch
 
 from .utils import Color, Observer, TorchUtils, X, Y
 
+UNCOLLIDABLE_JOINT_RENDERING_WIDTH = 1
+
 if TYPE_CHECKING:
     from .core import Entity
 
@@ -163,3 +165,20 @@ class JointConstraint:
 
     def pos_point(self, entity: "Entity"):
         return entity.state.pos + self.get_delta_anchor(entity)
+
+    def render(self, env_index: int = 0):
+        """joints.py:217-241: a line of the joint's length between the two anchor points."""
+        if self.dist == 0:
+            return []
+        import math
+
+        from . import rendering
+
+        ends = torch.stack([self.pos_point(self.entity_a)[env_index], self.pos_point(self.entity_b)[env_index]]).tolist()
+        (ax, ay), (bx, by) = ends
+        line = rendering.Line((-self.dist / 2, 0), (self.dist / 2, 0), width=UNCOLLIDABLE_JOINT_RENDERING_WIDTH)
+        xform = rendering.Transform()
+        xform.set_translation((ax + bx) / 2, (ay + by) / 2)
+        xform.set_rotation(math.atan2(by - ay, bx - ax))
+        line.add_attr(xform)
+        return [line]

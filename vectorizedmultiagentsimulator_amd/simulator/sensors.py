@@ -36,7 +36,7 @@ class Sensor(ABC):
         raise NotImplementedError
 
     def render(self, env_index: int = 0):
-        raise NotImplementedError("rendering is not part of the MI355X engine")
+        raise NotImplementedError
 
     def to(self, device: torch.device):
         raise NotImplementedError
@@ -134,3 +134,36 @@ class Lidar(Sensor):
 
     def set_render(self, render: bool):
         self._render = render
+
+    def render(self, env_index: int = 0):
+        """sensors.py:127-161: per ray a black line to the hit point and a small disc on it."""
+        if not self._render or self._last_measurement is None:
+            return []
+        import math
+
+        from . import rendering
+        from ._render import host_value
+
+        agent = self.agent
+        pos = host_value(agent, "pos", env_index, lambda: agent.state.pos[env_index])
+        rot = host_value(agent, "rot", env_index, lambda: agent.state.rot[env_index])[0]
+        angles = host_value(self, "angles", env_index, lambda: self._angles[env_index])
+        dists = host_value(self, "dist", env_index, lambda: self._last_measurement[env_index])
+        px, py = pos
+        geoms = []
+        for angle, dist in zip(angles, dists):
+            angle = angle + rot
+            ray = rendering.Line((0, 0), (dist, 0), width=0.05)
+            xform = rendering.Transform()
+            xform.set_translation(px, py)
+            xform.set_rotation(angle)
+            ray.add_attr(xform)
+            ray.set_color(r=0, g=0, b=0, alpha=self.alpha)
+            ray_circ = rendering.make_circle(0.01)
+            ray_circ.set_color(*self.render_color, alpha=self.alpha)
+            xform = rendering.Transform()
+            xform.set_translation(px + math.cos(angle) * dist, py + math.sin(angle) * dist)
+            ray_circ.add_attr(xform)
+            geoms.append(ray)
+            geoms.append(ray_circ)
+        return geoms
