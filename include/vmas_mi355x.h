@@ -46,8 +46,9 @@ extern "C" {
  *     the fused programs' out_delta (direct outputs) and VMAS_COPY_STORE64 spans
  * v7: VmasDiscreteActionRef, vmas_apply_discrete_actions / _launch
  * v8: VmasRenderPrim / VmasRenderEntity / VmasRenderLidar / VmasRenderScene, vmas_render_frames,
- *     vmas_render_scene */
-#define VMAS_ABI_VERSION 8
+ *     vmas_render_scene
+ * v9: VmasMaskedSpan / vmas_masked_rows, VmasBalanceResetIO / vmas_balance_reset */
+#define VMAS_ABI_VERSION 9
 
 /* error codes */
 #define VMAS_OK 0
@@ -1015,6 +1016,65 @@ int32_t vmas_render_scene(int32_t device, int32_t n_frames, const int64_t* env_i
                           const VmasRenderLidar* lidars, int32_t n_lidars,
                           const VmasRenderScene* scene, VmasRenderPrim* prims, float* verts,
                           float* bounds, void* stream);
+
+/* ---- masked batch reset (v9; Environment.reset_where) ----------------------------------------------
+ * vmas_masked_rows <- the per-row merge that Environment._reset_at makes through
+ * TorchUtils.where_from_index (vmas/simulator/environment/environment.py:229-262 `_reset_at`;
+ * vmas/simulator/utils.py:233-240 `where_from_index`, called from the state containers' `_reset`
+ * in vmas/simulator/core.py), for a whole mask of environments at once.
+ * Row b of a span is the row_bytes contiguous bytes at dst + b * dst_stride (src + b * src_stride).
+ * DIRECTION: row b is copied src -> dst for every b with (mask[b] != 0) == (copy_if_set != 0); the
+ * other rows of dst -- and every row of src -- are left as they are.  reset_where passes the tensors
+ * a full reset left as dst, the tensors from before it as src and copy_if_set = 0: the envs outside
+ * the mask get their old rows back.  One launch for up to VMAS_MASKED_MAX_SPANS spans (more take
+ * several); consecutive threads take consecutive 16- / 8- / 4- / 1-byte units of a row and then the
+ * next row, so a contiguous [B, k] tensor is read and written in whole lines.  mask: batch bytes
+ * (torch.bool).  device == -1: the same loop on the host. */
+#define VMAS_MASKED_MAX_SPANS 96 /* (96 x 40 B as kernel arguments) */
+typedef struct VmasMaskedSpan {
+    void* dst;
+    const void* src;
+    int64_t row_bytes;
+    int64_t dst_stride, src_stride; /* bytes from one row to the next */
+} VmasMaskedSpan;
+int32_t vmas_masked_rows(int32_t device, const VmasMaskedSpan* spans, int32_t n, const uint8_t* mask, int64_t batch,
+                         int32_t copy_if_set, void* stream);
+
+/* vmas_balance_reset <- Scenario.reset_world_at(None) of balance (vmas/scenarios/balance.py:85-215
+ * `reset_world_at`, after World.reset, core.py) for the rows of a mask, in place: one thread per env;
+ * a row outside the mask is neither read nor written.  A masked row b draws element b of the four
+ * uniform_ calls of the full reset (goal x, goal y, line x, package offset on [B, 1] tensors: column j
+ * at generator offset `offset` + j * increment, bounds lo[j] / hi[j]; mode as vmas_uniform_columns),
+ * places every entity with the reference's fp32 additions, zeroes vel / rot / ang_vel of every entity
+ * and force / torque of every agent, computes on_the_ground and global_shaping with the fused
+ * program's arithmetic (csrc/vmas_programs.hpp) and sets steps[b] = 0.  *increment: what the four
+ * calls advance the generator by (the caller adds it). */
+typedef struct VmasMutVec { /* element (b, k) at p[b * s0 + k * s1]; p NULL: absent */
+    float* p;
+    int32_t s0, s1;
+} VmasMutVec;
+typedef struct VmasResetEntity {
+    VmasMutVec pos, vel, rot, ang_vel;
+} VmasResetEntity;
+typedef struct VmasBalanceResetIO {
+    int32_t batch, n_agents, mode, pad0;
+    uint64_t seed, offset;
+    const uint8_t* mask;  /* [B] torch.bool */
+    float lo[4], hi[4];   /* f32 bounds of the draws, in draw order */
+    float line_y;         /* f32(-y_semidim + 2 * agent_radius) */
+    float package_rel_y;  /* f32(package radius) */
+    float floor_x, floor_y;
+    float agent_dy;       /* f32(-2 * agent_radius) */
+    float shaping_factor;
+    float floor_length, floor_width, line_length, package_radius_lmd; /* as VmasShapeRef */
+    float agent_dx[VMAS_SCN_MAX_AGENTS]; /* f32 of the python offsets along the line */
+    VmasResetEntity goal, package, line, floor, agents[VMAS_SCN_MAX_AGENTS];
+    VmasMutVec force[VMAS_SCN_MAX_AGENTS], torque[VMAS_SCN_MAX_AGENTS];
+    uint8_t* on_the_ground; /* [B] torch.bool, contiguous */
+    VmasMutVec global_shaping; /* [B] */
+    float* steps;              /* [B] contiguous, or NULL */
+} VmasBalanceResetIO;
+int32_t vmas_balance_reset(int32_t device, const VmasBalanceResetIO* io, uint64_t* increment, void* stream);
 
 #ifdef __cplusplus
 }

@@ -19,7 +19,7 @@ LIB_PATH = Path(os.environ.get("VMAS_LIB_PATH") or Path(__file__).resolve().pare
 
 # ------------------------------------------------------------------------------------------------
 # constants mirrored from include/vmas_mi355x.h
-VMAS_ABI_VERSION = 8
+VMAS_ABI_VERSION = 9
 VMAS_SPHERE, VMAS_BOX, VMAS_LINE = 0, 1, 2
 (
     VMAS_PAIR_JOINT,
@@ -127,6 +127,8 @@ EXPORTED_SYMBOLS = (
     "vmas_jit_last_error",
     "vmas_render_frames",
     "vmas_render_scene",
+    "vmas_masked_rows",
+    "vmas_balance_reset",
 )
 
 _i32 = ctypes.c_int32
@@ -412,6 +414,54 @@ class VmasBalanceIO(ctypes.Structure):
     ]
 
 
+# masked batch reset (csrc/vmas_copy.hip k_masked_rows, csrc/vmas_reset.hip k_balance_reset)
+VMAS_MASKED_MAX_SPANS = 96
+MASKED_SPAN_DTYPE = np.dtype([("dst", np.uint64), ("src", np.uint64), ("row_bytes", np.int64),
+                              ("dst_stride", np.int64), ("src_stride", np.int64)])  # VmasMaskedSpan
+
+
+class VmasMaskedSpan(ctypes.Structure):
+    _fields_ = [("dst", _vp), ("src", _vp), ("row_bytes", ctypes.c_int64), ("dst_stride", ctypes.c_int64),
+                ("src_stride", ctypes.c_int64)]
+
+
+def masked_rows(device_index: int, spans, mask_ptr: int, batch: int, copy_if_set: bool, stream) -> None:
+    """One native launch (vmas_masked_rows) for every (dst_ptr, src_ptr, row_bytes, dst_stride,
+    src_stride) span: row b goes src -> dst where (mask[b] != 0) == copy_if_set.  device_index -1:
+    the host loop over host pointers."""
+    n = len(spans)
+    if not n:
+        return
+    tbl = np.array(spans, dtype=np.uint64)  # [n, 5]: the rows of MASKED_SPAN_DTYPE (every field 8 bytes, >= 0)
+    assert tbl.shape == (n, 5)
+    check_aux(load_library().vmas_masked_rows(device_index, tbl.ctypes.data, n, mask_ptr, batch, int(bool(copy_if_set)),
+                                              stream), "vmas_masked_rows")
+
+
+class VmasMutVec(ctypes.Structure):
+    _fields_ = [("p", _vp), ("s0", _i32), ("s1", _i32)]
+
+
+class VmasResetEntity(ctypes.Structure):
+    _fields_ = [("pos", VmasMutVec), ("vel", VmasMutVec), ("rot", VmasMutVec), ("ang_vel", VmasMutVec)]
+
+
+class VmasBalanceResetIO(ctypes.Structure):
+    _fields_ = [
+        ("batch", _i32), ("n_agents", _i32), ("mode", _i32), ("pad0", _i32),
+        ("seed", ctypes.c_uint64), ("offset", ctypes.c_uint64), ("mask", _vp),
+        ("lo", _f32 * 4), ("hi", _f32 * 4),
+        ("line_y", _f32), ("package_rel_y", _f32), ("floor_x", _f32), ("floor_y", _f32), ("agent_dy", _f32),
+        ("shaping_factor", _f32),
+        ("floor_length", _f32), ("floor_width", _f32), ("line_length", _f32), ("package_radius_lmd", _f32),
+        ("agent_dx", _f32 * VMAS_SCN_MAX_AGENTS),
+        ("goal", VmasResetEntity), ("package", VmasResetEntity), ("line", VmasResetEntity), ("floor", VmasResetEntity),
+        ("agents", VmasResetEntity * VMAS_SCN_MAX_AGENTS),
+        ("force", VmasMutVec * VMAS_SCN_MAX_AGENTS), ("torque", VmasMutVec * VMAS_SCN_MAX_AGENTS),
+        ("on_the_ground", _vp), ("global_shaping", VmasMutVec), ("steps", _vp),
+    ]
+
+
 class VmasRayTarget(ctypes.Structure):
     _fields_ = [("shape", _i32), ("radius", _f32), ("length", _f32), ("width", _f32), ("pos", _vp), ("rot", _vp),
                 ("pos_s0", _i32), ("pos_s1", _i32), ("rot_s0", _i32), ("pad", _i32)]
@@ -650,6 +700,10 @@ def load_library(path: os.PathLike | str | None = None) -> ctypes.CDLL:
     lib.vmas_copy_spans_draw.restype = _i32
     lib.vmas_copy_spans_draw.argtypes = [_i32, _vp, _i32, ctypes.c_int64, _vp, _i32, ctypes.c_uint64, ctypes.c_uint64,
                                          _vp, _i32, ctypes.c_int64, ctypes.POINTER(ctypes.c_uint64), _vp]
+    lib.vmas_masked_rows.restype = _i32
+    lib.vmas_masked_rows.argtypes = [_i32, _vp, _i32, _vp, ctypes.c_int64, _i32, _vp]
+    lib.vmas_balance_reset.restype = _i32
+    lib.vmas_balance_reset.argtypes = [_i32, _vp, ctypes.POINTER(ctypes.c_uint64), _vp]
     lib.vmas_stream_abort_capture.restype = _i32
     lib.vmas_stream_abort_capture.argtypes = [_vp]
     lib.vmas_graph_launch.restype = _i32

@@ -7,11 +7,15 @@
 // dtype -- goes in ONE launch: blockIdx.y = span, blockIdx.x grid-strides over the span in 16-byte
 // (or, for unaligned spans, 4- / 1-byte) units, 256 threads x 4 units per workgroup round.
 // HBM-bound: 2 x bytes of traffic.
+//
+// Also k_masked_rows (vmas_masked_rows): per-row copies under a mask, the merge launch of
+// Environment.reset_where's generic path (simulator/environment/_masked.py).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 
 #include "vmas_aux.hpp"
 #include "vmas_mi355x.h"
@@ -109,6 +113,47 @@ constexpr int kFillThreads = 256;
 __global__ void __launch_bounds__(kFillThreads) k_fill_u32(uint32_t* __restrict__ dst, uint32_t value, int64_t n) {
     for (int64_t i = (int64_t)blockIdx.x * kFillThreads + threadIdx.x; i < n; i += (int64_t)gridDim.x * kFillThreads)
         dst[i] = value;
+}
+
+// ---- masked rows (vmas_masked_rows; Environment.reset_where) ------------------------------------
+// blockIdx.y = span; the span's batch x (row_bytes / unit) units are taken in order by consecutive
+// threads (grid-stride): the units of a row, then the next row -- whole lines of a contiguous [B, k]
+// tensor.  A row is copied src -> dst when (mask[row] != 0) == want; the others are not touched.
+struct MaskedArgs {
+    VmasMaskedSpan s[VMAS_MASKED_MAX_SPANS];
+    const uint8_t* mask;
+    long long batch;
+    int want;
+};
+static_assert(sizeof(MaskedArgs) <= 4096, "kernel argument block");
+
+__host__ __device__ __forceinline__ int masked_unit(const VmasMaskedSpan& s) {
+    const uintptr_t al = (uintptr_t)s.src | (uintptr_t)s.dst | (uintptr_t)s.row_bytes | (uintptr_t)s.dst_stride |
+                         (uintptr_t)s.src_stride;
+    return (al & 15) == 0 ? 16 : (al & 7) == 0 ? 8 : (al & 3) == 0 ? 4 : 1;
+}
+
+template <typename T>
+__device__ __forceinline__ void masked_units(const VmasMaskedSpan& s, const uint8_t* __restrict__ mask, long long batch,
+                                             bool want) {
+    const long long k = s.row_bytes / (long long)sizeof(T), n = batch * k;
+    const long long step = (long long)gridDim.x * kCopyThreads;
+    for (long long i = (long long)blockIdx.x * kCopyThreads + threadIdx.x; i < n; i += step) {
+        const long long row = k == 1 ? i : i / k, c = k == 1 ? 0 : i - row * k;
+        if ((mask[row] != 0) != want) continue;
+        const T v = *reinterpret_cast<const T*>(static_cast<const char*>(s.src) + row * s.src_stride + c * (long long)sizeof(T));
+        *reinterpret_cast<T*>(static_cast<char*>(s.dst) + row * s.dst_stride + c * (long long)sizeof(T)) = v;
+    }
+}
+
+__global__ void __launch_bounds__(kCopyThreads) k_masked_rows(MaskedArgs a) {
+    const VmasMaskedSpan s = a.s[blockIdx.y];
+    switch (masked_unit(s)) {
+        case 16: masked_units<uint4>(s, a.mask, a.batch, a.want != 0); break;
+        case 8: masked_units<uint2>(s, a.mask, a.batch, a.want != 0); break;
+        case 4: masked_units<uint32_t>(s, a.mask, a.batch, a.want != 0); break;
+        default: masked_units<uint8_t>(s, a.mask, a.batch, a.want != 0); break;
+    }
 }
 
 }  // namespace
@@ -216,5 +261,52 @@ extern "C" int32_t vmas_copy_spans_draw(int32_t device, const VmasCopySpan* span
     hipLaunchKernelGGL(k_copy_draw, dim3((unsigned)total), dim3(kCopyThreads), 0, (hipStream_t)stream, a);
     VMAS_AUX_HIP(hipGetLastError());
     *increment = inc * (unsigned long long)n_cols;
+    return VMAS_OK;
+}
+
+extern "C" int32_t vmas_masked_rows(int32_t device, const VmasMaskedSpan* spans, int32_t n, const uint8_t* mask,
+                                    int64_t batch, int32_t copy_if_set, void* stream) {
+    if (n < 0 || (n > 0 && !spans) || batch < 0 || (batch > 0 && !mask) || device < -1)
+        return vmas_aux::fail(VMAS_E_INVALID, "vmas_masked_rows: bad arguments");
+    for (int i = 0; i < n; ++i) {
+        const VmasMaskedSpan& s = spans[i];
+        // (rows of one tensor must not overlap: a stride shorter than the row would make the result
+        // depend on the order of the copies)
+        if (s.row_bytes < 0 || (s.row_bytes > 0 && (!s.dst || !s.src)) || s.dst_stride < s.row_bytes ||
+            s.src_stride < 0)
+            return vmas_aux::fail(VMAS_E_INVALID, "vmas_masked_rows: bad span %d", i);
+    }
+    const bool want = copy_if_set != 0;
+    if (device < 0) {  // the host backend: the same loop over host pointers
+        for (int i = 0; i < n; ++i) {
+            const VmasMaskedSpan& s = spans[i];
+            if (s.row_bytes == 0) continue;
+            for (int64_t b = 0; b < batch; ++b)
+                if ((mask[b] != 0) == want)
+                    memmove(static_cast<char*>(s.dst) + b * s.dst_stride, static_cast<const char*>(s.src) + b * s.src_stride,
+                            (size_t)s.row_bytes);
+        }
+        return VMAS_OK;
+    }
+    if (batch == 0) return VMAS_OK;
+    VMAS_AUX_HIP(hipSetDevice(device));
+    for (int first = 0; first < n; first += VMAS_MASKED_MAX_SPANS) {
+        MaskedArgs a{};
+        int m = 0;
+        int64_t most = 0;  // units of the largest span: sets the grid
+        for (int i = first; i < std::min(n, first + VMAS_MASKED_MAX_SPANS); ++i) {
+            const VmasMaskedSpan& s = spans[i];
+            if (s.row_bytes == 0) continue;
+            a.s[m++] = s;
+            most = std::max<int64_t>(most, batch * (s.row_bytes / masked_unit(s)));
+        }
+        if (m == 0) continue;
+        a.mask = mask;
+        a.batch = batch;
+        a.want = want ? 1 : 0;
+        const int gx = (int)std::max<int64_t>(1, std::min<int64_t>(kMaxCopyBlocks, (most + kCopyThreads - 1) / kCopyThreads));
+        hipLaunchKernelGGL(k_masked_rows, dim3(gx, m), dim3(kCopyThreads), 0, (hipStream_t)stream, a);
+        VMAS_AUX_HIP(hipGetLastError());
+    }
     return VMAS_OK;
 }

@@ -27,6 +27,7 @@
 
 #include "vmas_aux.hpp"
 #include "vmas_mi355x.h"
+#include "vmas_uniform.hpp"
 
 namespace vmas_aux {
 
@@ -154,55 +155,11 @@ __global__ void __launch_bounds__(256) k_spawn_resolve(SpawnArgs a, int32_t* out
 // ---- the respawn loop of several entities, tries drawn on the device (vmas_spawn_targets) --------
 constexpr int kUniformThreads = 256;  // PyTorch's distribution kernel block (vmas_actions.hip)
 
-struct DrawGrid {
-    long long step;  // threads of torch's uniform_ grid on B elements
-    unsigned long long inc;
-};
-
-// rocrand's philox4x32-10 block function (rocrand_philox4x32_10.h ten_rounds / single_round).
-__device__ __forceinline__ uint4 philox10(uint4 c, uint2 k) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        // (the 64-bit products: one v_mad_u64_u32 each instead of v_mul_hi_u32 + v_mul_lo_u32, both
-        // quarter rate)
-        const unsigned long long p0 = (unsigned long long)c.x * 0xD2511F53u;
-        const unsigned long long p1 = (unsigned long long)c.z * 0xCD9E8D57u;
-        const unsigned int hi0 = (unsigned int)(p0 >> 32), lo0 = (unsigned int)p0;
-        const unsigned int hi1 = (unsigned int)(p1 >> 32), lo1 = (unsigned int)p1;
-        c = make_uint4(hi1 ^ c.y ^ k.x, lo1, hi0 ^ c.w ^ k.y, lo0);
-        k.x += 0x9E3779B9u;
-        k.y += 0xBB67AE85u;
-    }
-    return c;
-}
-
-// Element b of torch's uniform_(lo, hi) on B floats at generator offset `off`: PyTorch's
-// distribution kernel (k_uniform_columns of vmas_actions.hip, probed bit for bit against torch;
-// `mode` bit 0 fused (0, 1] mapping, bit 1 fused affine transform) has thread t = b % step draw
-// rocrand4 round q / 4 and take component q % 4, q = b / step, from a philox state initialised
-// at (seed, subsequence t, offset off).  That state is counter (off / 4 + round, t) under key
-// seed, its 4 outputs shifted by off % 4 into the next block (rocrand's interleave); computed
-// here directly, one block function per draw.
-__device__ __forceinline__ float uniform_at(unsigned long long seed, unsigned long long off, const DrawGrid& g, int b,
-                                            float lo, float hi, int mode) {
-    const int step = (int)g.step, t = b % step, q = b / step;
-    const unsigned long long c = off / 4 + (unsigned long long)(q / 4);
-    const uint2 key = make_uint2((unsigned int)seed, (unsigned int)(seed >> 32));
-    const uint4 cur = philox10(make_uint4((unsigned int)c, (unsigned int)(c >> 32), (unsigned int)t, 0u), key);
-    const int sub = (int)(off & 3ull), k = sub + q % 4;
-    unsigned int u;
-    if (k < 4) {
-        u = k == 0 ? cur.x : k == 1 ? cur.y : k == 2 ? cur.z : cur.w;
-    } else {
-        const uint4 nxt = philox10(make_uint4((unsigned int)(c + 1), (unsigned int)((c + 1) >> 32), (unsigned int)t, 0u), key);
-        u = k == 4 ? nxt.x : k == 5 ? nxt.y : nxt.z;
-    }
-    const float inv = 2.3283064e-10f;  // ROCRAND_2POW32_INV
-    const float unit = (mode & 1) ? __builtin_fmaf((float)u, inv, inv) : inv + (float)u * inv;
-    const float range = hi - lo;
-    const float val = (mode & 2) ? __builtin_fmaf(unit, range, lo) : unit * range + lo;
-    return val == hi ? lo : val;  // (0, 1] -> [lo, hi)
-}
+// DrawGrid, philox10 and uniform_at -- element b of a torch uniform_ call, drawn directly -- live in
+// vmas_uniform.hpp (shared with the masked reset, vmas_reset.hip)
+using vmas_uniform::DrawGrid;
+using vmas_uniform::philox10;
+using vmas_uniform::uniform_at;
 
 // torch.cdist(...) < min_dist with cdist = sqrt(fl(fl(d0^2) + fl(d1^2))): sqrtf is correctly
 // rounded and monotone, so the test is d2 < d2_min, d2_min = the smallest float whose sqrtf

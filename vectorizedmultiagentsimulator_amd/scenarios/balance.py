@@ -112,6 +112,120 @@ class Scenario(BaseScenario):
         else:
             self.global_shaping[env_index] = dist[env_index] * self.shaping_factor
 
+    # ---- masked reset (Environment.reset_where; csrc/vmas_reset.hip k_balance_reset) ------------
+    # The rows of `mask` as reset_world_at(None) after World.reset leaves them, written in place by
+    # ONE launch: the four uniform_ columns above drawn per masked row at the offsets the full reset
+    # uses, the same fp32 additions, on_the_ground / global_shaping with the fused program's
+    # arithmetic, Environment.steps zeroed.  The device generator advances by the four calls.
+    native_resets = 0  # launches made (a test's proof that no fall-back ran)
+
+    @staticmethod
+    def _mut(t, dev):
+        """A [B, 2] / [B, 1] / [B] fp32 device tensor as a VmasMutVec, or None if it is not one."""
+        if (t is None or t.dtype is not torch.float32 or t.device != dev or t.dim() not in (1, 2)
+                or (t.dim() == 2 and t.shape[1] not in (1, 2)) or (t.shape[0] > 1 and t.stride(0) == 0)):
+            return None
+        v = N.VmasMutVec()
+        v.p, v.s0, v.s1 = t.data_ptr(), t.stride(0), (t.stride(1) if t.dim() > 1 else 0)
+        return v
+
+    def reset_world_where(self, mask):
+        from vectorizedmultiagentsimulator_amd.simulator.environment import _uniform
+
+        w = self.world
+        env = getattr(self, "_where_env", None)
+        A = len(w.agents)
+        if not _fused.enabled(w) or getattr(w, "_grad_enabled", False) or A > N.VMAS_SCN_MAX_AGENTS:
+            return NotImplemented
+        dev = torch.device(w.device)
+        if dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        B = w.batch_dim
+        mode = _uniform.mode(dev, B)
+        og, gs = getattr(self, "on_the_ground", None), getattr(self, "global_shaping", None)
+        if (mode is None or mask.dtype is not torch.bool or mask.device != dev or not mask.is_contiguous()
+                or og is None or og.dtype is not torch.bool or og.shape != (B,) or not og.is_contiguous()
+                or og.device != dev or gs is None or gs.shape != (B,)):
+            return NotImplemented
+        steps = env.steps if env is not None else None
+        if steps is not None and (steps.dtype is not torch.float32 or steps.shape != (B,) or not steps.is_contiguous()
+                                  or steps.device != dev):
+            return NotImplemented
+        # graph mode: the states as fresh tensors first (as any read of them makes them); a field
+        # still bound to the persistent action buffer (whose rows the next step's actions own)
+        # leaves the call to the generic path
+        p_buf = getattr(getattr(env, "_u_persist", None), "buffer", None)
+        p_lo = p_buf.data_ptr() if p_buf is not None else 0
+        p_hi = p_lo + 4 * p_buf.numel() if p_buf is not None else 0
+        io = N.VmasBalanceResetIO()
+        written = [og]
+        ok = True
+
+        def mut(t):
+            nonlocal ok
+            v = self._mut(t, dev)
+            if v is None or p_lo <= t.data_ptr() < p_hi:
+                ok = False
+                return N.VmasMutVec()
+            written.append(t)
+            return v
+
+        def entity(dst, e):
+            st = e.state
+            dst.pos, dst.vel, dst.rot, dst.ang_vel = mut(st.pos), mut(st.vel), mut(st.rot), mut(st.ang_vel)
+
+        entity(io.goal, self.package.goal)
+        entity(io.package, self.package)
+        entity(io.line, self.line)
+        entity(io.floor, self.floor)
+        half = self.line_length / 2
+        for i, a in enumerate(w.agents):
+            entity(io.agents[i], a)
+            if a.state.c is not None:
+                ok = False  # (communication state: not part of this scenario)
+            f, t = a.state.__dict__.get("_force"), a.state.__dict__.get("_torque")
+            io.force[i], io.torque[i] = mut(f), mut(t)
+            spacing = (self.line_length - a.shape.radius) / (self.n_agents - 1)
+            io.agent_dx[i] = -(self.line_length - a.shape.radius) / 2 + i * spacing
+        io.global_shaping = mut(gs)
+        # (one tensor bound to two fields -- a user's set_pos of a shared tensor -- cannot take two rows)
+        if not ok or len({t.data_ptr() for t in written}) != len(written):
+            return NotImplemented
+        pr = self.package.shape.radius
+        lo, hi = ((-half + pr, half - pr) if self.random_package_pos_on_line else (0.0, 0.0))
+        for j, (a, b) in enumerate(((-1.0, 1.0), (0.0, w.y_semidim), (-1.0 + half, 1.0 - half), (lo, hi))):
+            io.lo[j], io.hi[j] = a, b
+        io.batch, io.n_agents, io.mode = B, A, mode
+        io.line_y = -w.y_semidim + self.agent_radius * 2
+        io.package_rel_y = pr
+        io.floor_x, io.floor_y = 0.0, -w.y_semidim - self.floor.shape.width / 2 - self.agent_radius
+        io.agent_dy = -self.agent_radius * 2
+        io.shaping_factor = float(self.shaping_factor)
+        keep = []
+        fl, pk = _fused.ref(w, self.floor, keep, 0), _fused.ref(w, self.package, keep, 0)
+        io.floor_length, io.floor_width = fl.length, fl.width
+        io.line_length = _fused.ref(w, self.line, keep, 0).length
+        io.package_radius_lmd = pk.radius_lmd
+        io.mask = mask.data_ptr()
+        io.on_the_ground = og.data_ptr()
+        io.steps = steps.data_ptr() if steps is not None else None
+        gen = torch.cuda.default_generators[dev.index]
+        off = gen.get_offset()
+        io.seed, io.offset = gen.initial_seed(), off
+        inc = ctypes.c_uint64(0)
+        _fused.check(_fused.lib().vmas_balance_reset(dev.index, ctypes.byref(io), ctypes.byref(inc), _fused.stream(w)),
+                     "vmas_balance_reset")
+        gen.set_offset(off + inc.value)
+        for t in written:
+            _fused.bump_version(t)
+        if steps is not None:
+            _fused.bump_version(steps)
+            self._where_steps_done = True
+        for e in w.entities:
+            e.notify_observers()
+        self.native_resets += 1
+        return None
+
     def compute_on_the_ground(self):
         self.on_the_ground = self.world.is_overlapping(self.line, self.floor) + self.world.is_overlapping(
             self.package, self.floor

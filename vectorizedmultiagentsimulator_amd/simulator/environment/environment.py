@@ -257,6 +257,24 @@ class Environment(TorchVectorizedObject):
                               return_info=return_info, return_dones=return_dones)
 
     @local_seed(vmas_random_state)
+    def reset_where(self, mask=None, return_observations: bool = True, return_info: bool = False,
+                    return_dones: bool = False):
+        """Resets every env of ``mask`` in one call (no reference counterpart; the reference has
+        ``reset_at(index)``, one env per call).
+
+        :param mask: a bool tensor ``[num_envs]``, an integer index tensor, a sequence of ints, or
+            None: the envs that are done (``terminated | truncated`` with ``terminated_truncated``)
+
+        Rows of a full reset: with F the world ``reset()`` would leave if called now (the same
+        generator states, ``seed=None``), every batched state tensor afterwards holds F's row in
+        the envs of the mask and, bit for bit, its previous row elsewhere (``steps`` included), and
+        every generator is where ``reset()`` would leave it -- whatever the mask, an empty one too.
+        This is NOT the loop ``for i in mask.nonzero(): reset_at(i)``, whose draws for one env
+        depend on the tries of the envs before it.  Returns what ``reset_at`` returns."""
+        return self._reset_where(mask, return_observations=return_observations, return_info=return_info,
+                                 return_dones=return_dones)
+
+    @local_seed(vmas_random_state)
     def get_from_scenario(self, get_observations: bool, get_rewards: bool, get_infos: bool,
                           get_dones: bool, dict_agent_names: Optional[bool] = None):
         return self._get_from_scenario(get_observations=get_observations, get_rewards=get_rewards,
@@ -284,6 +302,24 @@ class Environment(TorchVectorizedObject):
         self._check_batch_index(index)
         self.scenario.env_reset_world_at(index)
         self.steps[index] = 0
+        result = self._get_from_scenario(get_observations=return_observations, get_infos=return_info,
+                                         get_rewards=False, get_dones=return_dones)
+        return result[0] if result and len(result) == 1 else result
+
+    def _reset_where(self, mask, return_observations=True, return_info=False, return_dones=False):
+        from . import _masked
+
+        if mask is None:
+            d = self._done()
+            mask = (d[0] | d[1]) if self.terminated_truncated else d
+        mask = _masked.as_mask(mask, self.num_envs, self.device)
+        g = self._graph
+        fr = g._fresh if g is not None else None
+        if fr is not None and fr.pending:
+            # (graph mode: the entity states as fresh tensors first, as any read of them makes them;
+            # in-place writes then reach the next replay by version counters, re-binds by identity)
+            fr.materialize()
+        self.scenario.env_reset_world_where(mask, self)
         result = self._get_from_scenario(get_observations=return_observations, get_infos=return_info,
                                          get_rewards=False, get_dones=return_dones)
         return result[0] if result and len(result) == 1 else result

@@ -49,6 +49,36 @@ class BaseScenario(ABC):
         self.world.reset(env_index)
         self.reset_world_at(env_index)
 
+    def env_reset_world_where(self, mask: Tensor, env=None):
+        # Do not override
+        """The reset of ``Environment.reset_where`` (no reference counterpart): after it every
+        batched state tensor holds, in the envs of ``mask`` (bool, [batch_dim]), the row a full
+        reset at the current generator states leaves, and elsewhere its previous row; the
+        generators advance as that full reset advances them.  ``reset_world_where`` does it when
+        the scenario has one; otherwise the full reset runs and its rows are merged
+        (environment/_masked.py).  ``env``: the Environment, whose ``steps`` take part."""
+        self._where_env = env
+        self._where_steps_done = False
+        try:
+            done = self.reset_world_where(mask) is not NotImplemented
+        finally:
+            self._where_env = None
+        if done:
+            if env is not None and not self._where_steps_done:
+                env.steps.masked_fill_(mask, 0)
+            return
+        from .environment._masked import generic_reset_where
+
+        generic_reset_where(self, mask, env)
+
+    def reset_world_where(self, mask: Tensor):
+        """Optional: reset the envs of ``mask`` (bool, [batch_dim]) with the semantics of
+        ``env_reset_world_where`` -- rows of the full reset, the generators advanced as by it.
+        Return ``NotImplemented`` (the default) to leave the call to the generic path.  An
+        implementation that also zeroes the step counter of ``self._where_env`` sets
+        ``self._where_steps_done = True``; otherwise the environment zeroes it."""
+        return NotImplemented
+
     def env_process_action(self, agent: Agent):
         # Do not override
         if agent.action_script is not None:
