@@ -44,7 +44,7 @@ bench("get_random_actions", env.get_random_actions)
 bench("before_actions", G.before_actions)
 bench("apply (speculative launch)", lambda: env._apply_continuous_actions(acts, persistent=True, speculative=True))
 bench("graph launch (raw)", G._launch)
-bench("post_replay", G._post_replay)
+bench("post_replay", G._stage.run)
 bench("check_device_errors", env.world.engine.check_device_errors)
 bench("_still_valid", G._still_valid)
 bench("current_stream", lambda: torch.cuda.current_stream(0))

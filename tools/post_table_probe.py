@@ -1,4 +1,4 @@
-"""What a graph-mode step's post-replay launch moves (StepGraph._post_table): output clones, the
+"""What a graph-mode step's post-replay launch moves (PostStage.table): output clones, the
 carry of re-bound state (Y -> X, with the attribute names), the next step's rollback backups, the
 direct-output offset words; bytes per row kind.
 usage: python tools/post_table_probe.py [scenario] [envs]
@@ -25,15 +25,15 @@ for _ in range(8):
 torch.cuda.synchronize()
 g = env._graph
 print(f"{scenario} {n_envs}: graph {env.graph_status} ({env.graph_reason})")
-t = g._post_table()
-tbl = t["tbl"]
-n_out, n_all = t["n_out"], t["n_all"]
+t = g._stage.table()
+tbl = t.tbl
+n_out, n_all = t.n_out, t.n_all
 out_b = int(sum(int(r["nbytes"]) for r in tbl[:n_out] if int(r["nbytes"]) > 0))
 rest = tbl[n_out:n_all]
-n_bk = t["n_bk"]
+n_bk = t.n_bk
 carry_rows = rest[:len(rest) - n_bk] if n_bk else rest
 bk_rows = rest[len(rest) - n_bk:] if n_bk else rest[:0]
-print(f"rows: {n_out} output (+ direct words / step counter), {len(carry_rows)} carry, {len(bk_rows)} backup; plain={t['plain']}")
+print(f"rows: {n_out} output (+ direct words / step counter), {len(carry_rows)} carry, {len(bk_rows)} backup; plain={t.plain}")
 print(f"bytes: outputs {out_b / 1e6:.2f} MB, carry {sum(int(r['nbytes']) for r in carry_rows) / 1e6:.2f} MB, "
       f"backups {sum(int(r['nbytes']) for r in bk_rows) / 1e6:.2f} MB")
 print("carried attributes:", getattr(g, "_carry_names", "?"))
@@ -43,4 +43,4 @@ print("own scenario:", _own_scenario(env.scenario), "; agent dynamics:",
               for a in env.world.agents}), "; write-only ys:", len(g._write_only_ys))
 print("in-place (backed up) tensors:", len(g._inplace), [tuple(x.shape) for x in g._inplace][:12])
 print("direct categories:", len(g._direct.enabled) if g._direct is not None else 0,
-      "; clone groups:", [(str(dt), tuple(sh), n) for dt, sh, n in g._clone_groups])
+      "; clone groups:", [(str(dt), tuple(sh), n) for dt, sh, n in g._stage.clone_groups])

@@ -14,7 +14,7 @@ import torch
 
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 from vectorizedmultiagentsimulator_amd import make_env  # noqa: E402
-from vectorizedmultiagentsimulator_amd.simulator.environment import _graph  # noqa: E402
+from vectorizedmultiagentsimulator_amd.simulator.environment import _graph, _post  # noqa: E402
 from vectorizedmultiagentsimulator_amd.simulator.environment.environment import Environment  # noqa: E402
 
 scenario = sys.argv[1] if len(sys.argv) > 1 else "balance"
@@ -64,7 +64,7 @@ def launch(self, *a, **k):
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
     stamp("replay0")
-    r = orig_launch(self, *a, **k)  # (a deferred kernel chain: launched later, by _post_replay)
+    r = orig_launch(self, *a, **k)  # (a deferred kernel chain: launched later, by PostStage.run)
     stamp("replay1")
     e1.record()
     events.append((e0, e1))
@@ -72,7 +72,7 @@ def launch(self, *a, **k):
 
 
 _graph.StepGraph._launch = launch
-wrap(_graph.StepGraph, "_post_replay", "clone0", "clone1")
+wrap(_post.PostStage, "run", "clone0", "clone1")
 wrap(_graph.StepGraph, "_finish_deferred", "deferred0", "deferred1")
 
 N = 100

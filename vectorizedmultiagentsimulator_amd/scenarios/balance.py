@@ -436,7 +436,7 @@ class Scenario(BaseScenario):
 
     def _vmas_tail_sources(self):
         """The tensors the fused program writes through (sc1, csrc/vmas_programs.hpp bal_reward): a
-        graph replay may copy them inside the same launch (environment/_graph.py _tail_ok)."""
+        graph replay may copy them inside the same launch (environment/_post.py _tail_admit)."""
         return [self.global_shaping, self.pos_rew, self.ground_rew]
 
 

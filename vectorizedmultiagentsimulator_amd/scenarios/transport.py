@@ -228,7 +228,7 @@ class Scenario(BaseScenario):
 
     def _vmas_tail_sources(self):
         """The tensors the fused program writes through (sc1, csrc/vmas_programs.hpp tr_reward_done):
-        a graph replay may copy them inside the same launch (environment/_graph.py _tail_ok)."""
+        a graph replay may copy them inside the same launch (environment/_post.py _tail_admit)."""
         return [t for p in self.packages for t in (p.dist_to_goal, p.on_goal, p.color, p.global_shaping)]
 
 

@@ -1,4 +1,5 @@
-"""HIP-graph replay of ``Environment.step`` (opt-in: ``make_env(..., graph_step=True)``).
+"""HIP-graph replay of ``Environment.step`` (the default on a ROCm device; opt out with
+``make_env(..., graph_step=False)`` or ``VMAS_GRAPH_STEP=0``).
 
 The reference's step is an eager tensor program: per step ~70 small kernels for balance
 (scenario rewards / observations / dones around the physics launch), each launched from Python.
@@ -50,6 +51,10 @@ What a replay must honour, and how:
     why).  Host state kept elsewhere (module globals, objects the tracker does not visit) stays
     a documented requirement: the benchmark scenarios keep all per-step state in device
     tensors; tests/test_graph.py checks replay == eager bit for bit.
+
+This module holds the capture, the carry plan, the watched trial step, the replay entry points and
+the rollback.  What runs after a replay -- the span table, the fresh outputs, the one copy launch --
+is ``_post.py`` (``PostStage``, one per capture).
 """
 from __future__ import annotations
 
@@ -66,6 +71,7 @@ from torch import Tensor
 
 from ... import _native as N
 from ..core import Agent
+from ._post import PostStage
 
 _VERSION = operator.attrgetter("_version")  # a tensor's version counter (map() without a Python frame)
 
@@ -426,6 +432,12 @@ class _KernelChain:
             return None, lib.vmas_last_error().decode(errors="replace")
         return cls(graph, out, lib.vmas_graph_chain_nodes(out), lib.vmas_graph_chain_fused(out)), ""
 
+    def launch(self, wb: bool, stream) -> None:
+        """The chain's kernels on the stream; wb: k_world's write-back variant (set_writeback)."""
+        lib = N.load_library()
+        fn = lib.vmas_graph_chain_launch_wb if wb else lib.vmas_graph_chain_launch
+        N.check(fn(self.handle, stream), "vmas_graph_chain_launch")
+
     def set_writeback(self, backup_delta: int) -> bool:
         """The write-back variant of the chain's k_world launch (vmas_graph_chain_set_writeback):
         False when the chain has no k_world launch."""
@@ -660,6 +672,9 @@ class _FreshState:
         return bool(spans)
 
 
+_WB_UNTRIED, _WB_REFUSED, _WB_ACTIVE = "untried", "refused", "active"
+
+
 class StepGraph:
     """Capture / replay state of one Environment (see the module docstring)."""
 
@@ -669,8 +684,6 @@ class StepGraph:
         self.status = "warming"
         self.eager_steps = 0
         self.replays = 0
-        self._out_tree = None
-        self._out_tensors: List[Tensor] = []
         self._carry_dst: List[Tensor] = []  # X (read by the graph)
         self._carry_src: List[Tensor] = []  # Y (written by the graph)
         self._watch: List[Tuple[dict, str, Tensor]] = []  # (obj.__dict__, key, bound tensor)
@@ -689,11 +702,12 @@ class StepGraph:
         self._holes: List[Tuple[Any, tuple, Tensor]] = []  # (fn, args, output) run after segment i
         self._executed = None  # outputs of a capture step that already ran (segmented capture)
         self._carry_ys: List[Tensor] = []  # the Y tensors as bound (version counters)
-        self._post: Optional[dict] = None  # what the last post-replay launch covered (_post_replay)
+        self._stage: Optional[PostStage] = None  # the capture's post-replay stage (_post.py)
         self._direct: Optional[DirectOutputs] = None  # (the capture's directly written outputs)
         # launches captured with their host side deferred (world._deferred_sink: discovery's
         # DeferredRespawn): armed before every replay, finished after its host work is queued
         self._deferred: List[Any] = []
+        self._device_rng_outside_holes = True  # (until a trial step shows otherwise: _trial)
         # Environment.steps += 1 (ref environment.py:397) folded into the post-replay launch (an
         # increment span of vmas_copy_spans) instead of a kernel node of the graph: set while the
         # capture records body(), kept for the captured graph (_steps_folded)
@@ -701,10 +715,11 @@ class StepGraph:
         self._steps_folded = False
         self._steps_t = None
         self._fresh: Optional[_FreshState] = None  # fresh entity states on first use after a replay
-        # the state write-back (_writeback_ready): the carry index of the engine's state buffer, and
-        # None (not tried) / False (not possible) / {chain, backup}
+        # the state write-back (_writeback_ready): the carry index of the engine's state buffer,
+        # whether it was tried, and while it is active the (chain, backup) it is set up for
         self._state_idx: Optional[int] = None
-        self._wb = None
+        self._wb_state = _WB_UNTRIED
+        self._wb_pair: Optional[Tuple[_KernelChain, Tensor]] = None
 
     # ---- the step -------------------------------------------------------------------------------
     def body(self):
@@ -732,7 +747,7 @@ class StepGraph:
         fr = self._fresh
         if fr is not None and fr.bound is not None and fr.unbind():
             self.copied = True  # (Y written from F: the carry Y -> X runs again)
-            self._post = None
+            self._stage.invalidate()
         self.env.world.engine.check_device_errors()
         if not self._still_valid():
             self.drop("world or entity parameters changed")
@@ -764,9 +779,9 @@ class StepGraph:
                             return
                 d[k] = t
                 self.copied = True
-        if not self._first_replay and not self._carry_current():
+        if not self._first_replay and not self._stage.carry_current():
             self.copied = True
-            self._post = None
+            self._stage.invalidate()
             with torch.no_grad():
                 if self._carry_dst:
                     N.copy_spans(self._dev_index(), list(zip(self._carry_dst, self._carry_src)), self._stream())
@@ -781,7 +796,7 @@ class StepGraph:
                 if self.eager_steps >= WARM_STEPS:
                     if self._capture():
                         if self._executed is not None:  # a segmented capture ran the step already
-                            out, self._executed = self._clone_outputs(), None
+                            out, self._executed = self._stage.clone_outputs(), None
                             self._asserts.after_replay(self.env.device)
                             return out
                         return self._replay()
@@ -876,20 +891,6 @@ class StepGraph:
                         + ", ".join(f"{names.get(i, '?')}.{k}" for i, k in changed[:4]))[:300]
         return out
 
-    _AHEAD_DEFERRED = os.environ.get("VMAS_GRAPH_DRAW_AHEAD_DEFERRED", "1") != "0"  # (A/B knob)
-
-    def _ahead_offset_word(self):
-        """Where a draw made ahead in the post-replay launch reads its generator offset: 0 (the
-        host passes it) without deferred launches; with one spawn channel (discovery's respawn,
-        whose host side advances the generator only after this launch is queued) the device word
-        the respawn launch leaves it in (VMAS_SPAWN_OFF_END_WORD); None: no draw ahead."""
-        if not self._deferred:
-            return 0
-        if len(self._deferred) != 1 or not self._AHEAD_DEFERRED:
-            return None
-        mx = getattr(getattr(self._deferred[0], "chan", None), "mx", None)
-        return None if mx is None else mx.data_ptr() + 4 * N.VMAS_SPAWN_OFF_END_WORD
-
     def _finish_deferred(self, apply: bool = True, out=None):
         """The host side of the captured deferred launches (discovery's respawn).  One that had to
         be redone on the host (DeferredRespawn.finish) changed state the graph's observations had
@@ -936,23 +937,20 @@ class StepGraph:
         self.status = "dropped"
         self.why = why
         self.eager_steps = 0
-        self._out_tree = None
-        self._out_tensors = []
         self._carry_dst, self._carry_src, self._watch = [], [], []
-        self._state_idx, self._wb = None, None
+        self._state_idx = None
+        self._wb_state, self._wb_pair = _WB_UNTRIED, None
         self._watch_cols = None
-        self._carry_ys, self._post = [], None
+        self._carry_ys, self._stage = [], None
         self._steps_folded = False
 
     # ---- capture --------------------------------------------------------------------------------
-    _FOLD_STEPS = os.environ.get("VMAS_GRAPH_FOLD_STEPS", "1") != "0"  # (A/B knob)
-
     def _fold_steps_ok(self) -> bool:
         """Whether the capture leaves `steps += 1` to the post-replay launch: nothing in the
         captured step reads steps (no max_steps: the done program reads it, ref
         environment.py:415-418) and it is a contiguous fp32 tensor on the step's device."""
         st = getattr(self.env, "steps", None)
-        return (self._FOLD_STEPS and self.env.max_steps is None and isinstance(st, Tensor)
+        return (self.env.max_steps is None and isinstance(st, Tensor)
                 and st.dtype is torch.float32 and st.is_contiguous() and st.device.type == "cuda")
 
     def _capture(self) -> bool:
@@ -990,7 +988,7 @@ class StepGraph:
         contents = [(t, t.clone()) for t, _ in versions.values()
                     if not any(st == 0 and n > 1 for st, n in zip(t.stride(), t.shape))]
         segs = _Segments(side)
-        self._direct = DirectOutputs(dev) if self._DIRECT else None
+        self._direct = DirectOutputs(dev)
         deferred: List[Any] = []
 
         def deferred_sink(d):  # captured here; armed / finished around each replay
@@ -1002,7 +1000,7 @@ class StepGraph:
             env.world._assert_range_sink = asserts.capture_range
             env.world._hole_sink = segs.hole
             # (the deferred form only when the step draws no other device random numbers)
-            env.world._deferred_sink = None if getattr(self, "_device_rng_outside_holes", True) else deferred_sink
+            env.world._deferred_sink = None if self._device_rng_outside_holes else deferred_sink
             env.world._direct_out = self._direct
             torch.cuda.synchronize(dev)
             self._folding = self._fold_steps_ok()
@@ -1017,17 +1015,20 @@ class StepGraph:
             self._consts = consts
             self._asserts = asserts
             self._sig = eng.graph_token()
-            if self._direct is not None and not segs.holes:  # (a segmented step keeps its copies)
+            if not segs.holes:  # (a segmented step keeps its copies)
                 self._direct.finalize(_tensors(out, []), env.scenario)
-            self._plan(objs, snap, out)
-            if self._direct is not None:
-                self._direct.arm(N.stream_ptr(self._dev_index()))
+            out_tensors = self._plan(objs, snap, out)
+            self._direct.arm(N.stream_ptr(self._dev_index()))
             self._inplace = [t for t, v in versions.values() if t._version != v]
             ids = {id(t) for t in self._inplace}
             self._inplace += [y for y in self._write_only_ys if id(y) not in ids]
-            self._bk_src: List[Tensor] = []
-            self._bk_dst: List[Tensor] = []
-            self._bk_u = None
+            self._bk_src, self._bk_dst, self._bk_u = [], [], None
+            self._stage = PostStage(
+                env=env, dev_index=self._dev_index(), out_tree=out, out_tensors=out_tensors,
+                carry_dst=self._carry_dst, carry_src=self._carry_src, carry_other=self._carry_other,
+                carry_ys=self._carry_ys, inplace=self._inplace, state_idx=self._state_idx,
+                direct=self._direct.enabled, steps_folded=self._folding, deferred=deferred,
+                tail=self._TAIL and _trusted_scenario(env.scenario))
         except Exception as ex:  # noqa: BLE001 -- any capture failure means "stay eager"
             # a capture invalidated by a forbidden call may be left open: end it, so that the
             # eager step that follows can launch
@@ -1048,7 +1049,7 @@ class StepGraph:
             self.status = "eager"
             self.why = f"{type(ex).__name__}: {str(ex).splitlines()[0] if str(ex) else ''}"[:300]
             self.graph = None
-            self._direct = None
+            self._direct = self._stage = None
             self._folding = False
             return False
         finally:
@@ -1086,17 +1087,18 @@ class StepGraph:
         self.why = ""
         self._first_replay = not segs.holes
         self._executed = out if segs.holes else None
-        self._post = None
         return True
 
-    def _plan(self, objs, snap, out):
+    def _plan(self, objs, snap, out) -> List[Tensor]:
+        """The carry plan and the watch list of a capture; returns the step's output tensors as
+        the post-replay stage copies them."""
         carry: List[Tuple[Tensor, Tensor]] = []
         names: List[str] = []
         state_field: List[bool] = []  # (an entity state's pos / vel / rot / ang_vel: what k_world integrates)
         fresh = []  # carried entity-state attributes: re-bound to fresh tensors on first use (_FreshState)
         # re-bound attributes no step reads before re-binding them (the package's own scenarios and
         # sensors declare them): not carried; a rollback restores them from the backups (_inplace)
-        own = self._WRITE_ONLY and _trusted_scenario(self.env.scenario)
+        own = _trusted_scenario(self.env.scenario)
         self._write_only_ys = []
         for o, before in snap:
             after = o.__dict__
@@ -1155,7 +1157,8 @@ class StepGraph:
         # one multi-tensor copy kernel: contiguous pairs as flat byte views (one dtype), the rest
         # (non-contiguous views) copied one by one
         self._carry_dst, self._carry_src, self._carry_other = [], [], []
-        self._state_idx, self._wb = None, None
+        self._state_idx = None
+        self._wb_state, self._wb_pair = _WB_UNTRIED, None
         for x, y in zip(dst, src):
             if x.is_contiguous() and y.is_contiguous() and x.dtype == y.dtype:
                 if state_pair is not None and x is state_pair[0]:
@@ -1175,12 +1178,11 @@ class StepGraph:
         self._watch_cols = (tuple(d for d, _, _ in self._watch), tuple(k for _, k, _ in self._watch),
                             tuple(t for _, _, t in self._watch))
         self._fresh_items = fresh
-        self._out_tree = out
         # an output marked constant (BaseScenario.done's all-False view of one element made outside
         # the capture, which no replay writes) is copied from a contiguous copy made once here:
         # part of the post-replay launch instead of a strided torch copy per step
-        self._out_tensors = [t.contiguous() if getattr(t, "_vmas_constant", False) and not t.is_contiguous() else t
-                             for t in _tensors(out, [])]
+        return [t.contiguous() if getattr(t, "_vmas_constant", False) and not t.is_contiguous() else t
+                for t in _tensors(out, [])]
 
     def _still_valid(self) -> bool:
         return self.env.world.engine.graph_token() == self._sig
@@ -1203,9 +1205,9 @@ class StepGraph:
                     fn(*args, out=res)
             return
         if self._chain is not None:  # the graph's kernels as plain launches (_KernelChain)
-            if defer_chain:  # (launched by the post-replay call: _post_replay(chain=...))
+            if defer_chain:  # (launched by the post-replay call: PostStage.run(chain=...))
                 return self._chain
-            self._launch_chain(self._chain, wb)
+            self._chain.launch(wb, self._stream())
             return
         if self._raw_exec is not None:
             N.check(N.load_library().vmas_graph_launch(self._raw_exec, N.stream_ptr(self._dev_index())),
@@ -1215,24 +1217,16 @@ class StepGraph:
         gen = torch.cuda.default_generators[dev.index if dev.index is not None else torch.cuda.current_device()]
         before = gen.get_offset()
         self.graph.replay()
-        if self.replays == 0 and gen.get_offset() == before and self._RAW_LAUNCH:
+        if self.replays == 0 and gen.get_offset() == before:
             self._raw_exec = ctypes.c_void_p(self.graph.raw_cuda_graph_exec())
             self._chain, self.chain_why = _KernelChain.build(self.graph) if self._CHAIN else (None, "off")
 
-    _RAW_LAUNCH = os.environ.get("VMAS_GRAPH_RAW_LAUNCH", "1") != "0"  # (A/B knob)
     # a replay whose graph is a short chain of kernel nodes launches them on the stream instead
     # (_KernelChain); 0: hipGraphLaunch (A/B knob)
     _CHAIN = os.environ.get("VMAS_GRAPH_CHAIN", "1") != "0"
-    # a pre-applied replay's kernel chain launched by the post-replay C++ call (_vmas_host post /
-    # post_draw) instead of its own ctypes call; 0: launched from Python first (A/B knob)
-    _CHAIN_IN_POST = os.environ.get("VMAS_GRAPH_CHAIN_IN_POST", "1") != "0"
-    # fused programs write the step's outputs into fresh tensors (DirectOutputs); 0: copied out
-    _DIRECT = os.environ.get("VMAS_GRAPH_DIRECT_OUTPUTS", "1") != "0"
     # fresh entity-state tensors on first use after each replay (_FreshState); 0: the states stay
     # views of the graph's buffers (an alias kept across a step then sees later steps' values)
     _FRESH_STATES = os.environ.get("VMAS_GRAPH_FRESH_STATES", "1") != "0"
-    # declared write-only attributes (_write_only) are not carried between replays; 0: carried
-    _WRITE_ONLY = os.environ.get("VMAS_GRAPH_WRITE_ONLY", "1") != "0"
 
     def _replay(self):
         asserts = self._asserts is not None and bool(self._asserts.msgs)
@@ -1249,7 +1243,7 @@ class StepGraph:
                 self._finish_deferred(apply=False)
                 self._rollback(rng, restore_actions=False)
                 raise
-        out = self._post_replay()
+        out = self._stage.run()
         self._finish_deferred(out=out)
         return out
 
@@ -1262,9 +1256,9 @@ class StepGraph:
             self._bk_src = [*self._inplace] + ([u_buf] if u_buf is not None else [])
             self._bk_dst = [torch.empty_like(t) for t in self._bk_src]
             self._bk_u = u_buf
-            self._post = None
+            self._stage.set_backups(self._bk_src, self._bk_dst)
         n = len(self._bk_src) if u_buf is not None else len(self._inplace)
-        if n and not self._backup_current(n):
+        if n and not self._stage.backup_current(n):
             with torch.no_grad():
                 pairs = list(zip(self._bk_dst[:n], self._bk_src[:n]))
                 if all(d.is_contiguous() and s.is_contiguous() for d, s in pairs):
@@ -1283,9 +1277,10 @@ class StepGraph:
         generator snapshot, which only a rollback reads."""
         self._first_replay = False
         wb = self._writeback_ready()
-        chain = self._launch(defer_chain=self._CHAIN_IN_POST, wb=wb)
+        # (a kernel chain is launched by the post-replay C++ call, not by a ctypes call of its own)
+        chain = self._launch(defer_chain=True, wb=wb)
         self.replays += 1
-        out = self._post_replay(chain=chain, wb=wb)
+        out = self._stage.run(None, chain, wb)
         self._finish_deferred(out=out)
         return out
 
@@ -1307,12 +1302,12 @@ class StepGraph:
     _WRITEBACK_MAX_BYTES = float(os.environ.get("VMAS_GRAPH_WRITEBACK_MAX_MB", "6")) * (1 << 20)
 
     def _writeback_ready(self) -> bool:
-        w = self._wb
-        if w is not None and w is not False and w["chain"] is self._chain:
+        state = self._wb_state
+        if state is _WB_ACTIVE and self._wb_pair[0] is self._chain:
             return True
-        if w is False or self._chain is None:
+        if state is _WB_REFUSED or self._chain is None:  # (active for another chain: judged again)
             return False
-        self._wb = False
+        self._wb_state, self._wb_pair = _WB_REFUSED, None
         if (not self._WRITEBACK or self._state_idx is None or self._carry_other
                 or not _trusted_scenario(self.env.scenario)):
             return False
@@ -1322,8 +1317,28 @@ class StepGraph:
         backup = torch.empty_like(x)  # (the first pass's copy of the pre-step state, same offsets)
         if not self._chain.set_writeback(backup.data_ptr() - x.data_ptr()):
             return False
-        self._wb = {"chain": self._chain, "backup": backup}
+        self._wb_state, self._wb_pair = _WB_ACTIVE, (self._chain, backup)
         return True
+
+    # ---- reads kept for their readers -----------------------------------------------------------
+    @property
+    def _wb(self):  # read by bench.py (tail_bytes_per_env_step) and tests/test_graph.py
+        """None (not tried) / False (refused) / {"chain", "backup"} (active)."""
+        if self._wb_state is _WB_ACTIVE:
+            return {"chain": self._wb_pair[0], "backup": self._wb_pair[1]}
+        return False if self._wb_state is _WB_REFUSED else None
+
+    @staticmethod
+    def _cache_view(t):
+        return None if t is None else (None, None, None, None, {"tbl": t.tbl})
+
+    @property
+    def _post_cache(self):  # read by bench.py (tail_bytes_per_env_step): [4]["tbl"], the span rows
+        return self._cache_view(self._stage.tbl if self._stage is not None else None)
+
+    @property
+    def _post_cache_wb(self):  # read by bench.py (tail_bytes_per_env_step) and tests/test_graph.py
+        return self._cache_view(self._stage.tbl_wb if self._stage is not None else None)
 
     def replay_speculative(self, flags_ok):
         """Replays the step while the action kernel's flags are still in flight, then waits for
@@ -1341,7 +1356,7 @@ class StepGraph:
         self.replays += 1
         # the host side of the post-replay copies (fresh output tensors, span table) while the
         # action kernel's flags are still in flight; nothing is launched before they pass
-        prep = self._post_prepare()
+        prep = self._stage.prepare()
         if not flags_ok():
             self._asserts.after_replay(dev, raise_=False)
             self._finish_deferred(apply=False)
@@ -1354,12 +1369,12 @@ class StepGraph:
             self._rollback(rng, restore_actions=False)
             raise
         # only now: the post-replay carry overwrites X, which a rollback restores Y from
-        out = self._post_replay(prep)
+        out = self._stage.run(prep)
         self._finish_deferred(out=out)
         return out
 
     def _rollback(self, rng: Tensor, restore_actions: bool):
-        self._post = None
+        self._stage.invalidate()
         n = len(self._bk_src) if restore_actions else len(self._inplace)
         with torch.no_grad():
             if n:
@@ -1370,20 +1385,6 @@ class StepGraph:
                 y.copy_(x)
         torch.cuda.set_rng_state(rng, self.env.device)
 
-    # ---- copies after a replay -----------------------------------------------------------------
-    def _launch_chain(self, chain, wb: bool = False) -> None:
-        lib = N.load_library()
-        fn = lib.vmas_graph_chain_launch_wb if wb else lib.vmas_graph_chain_launch
-        N.check(fn(chain.handle, N.stream_ptr(self._dev_index())), "vmas_graph_chain_launch")
-
-    _chain_fn_addr = None
-
-    @classmethod
-    def _chain_fn(cls, wb: bool = False) -> int:
-        if cls._chain_fn_addr is None:
-            cls._chain_fn_addr = (N.fn_addr("vmas_graph_chain_launch"), N.fn_addr("vmas_graph_chain_launch_wb"))
-        return cls._chain_fn_addr[1 if wb else 0]
-
     def _dev_index(self) -> int:
         dev = torch.device(self.env.device)
         return dev.index if dev.index is not None else torch.cuda.current_device()
@@ -1391,318 +1392,6 @@ class StepGraph:
     def _stream(self):
         return N.stream_ptr(self._dev_index())
 
-    def _carry_current(self) -> bool:
-        """The last post-replay launch carried Y -> X and no Y was modified since (version
-        counters: a native replay bumps none, a caller's in-place edit or the re-bind copy of
-        before_actions bumps them)."""
-        p = self._post
-        return p is not None and p["carry_ver"] == tuple(map(_VERSION, self._carry_ys))
-
-    def _backup_current(self, n: int) -> bool:
-        p = self._post
-        return (p is not None and p["bk_n"] >= n and self._carry_current()
-                and p["bk_ver"] == tuple(map(_VERSION, self._inplace)))
-
-    def _post_spans(self, wb: bool = False):
-        """Per capture: the carry spans (Y -> X, contiguous byte views) and the backup spans of
-        the next step (in-place tensors and the action buffer -> their backups; a backup whose
-        tensor lies inside a carry destination X is taken from the matching bytes of Y, which
-        is what X holds once the carry has run).  None if a backup straddles a carry destination
-        or is not contiguous (then the backups stay in backup())."""
-        carry = [(y.data_ptr(), x.data_ptr(), x.numel()) for i, (x, y) in enumerate(zip(self._carry_dst, self._carry_src))
-                 if not (wb and i == self._state_idx)]  # (wb: k_world wrote the state back itself)
-        bk = []
-        n = len(self._bk_src) if self._bk_dst else 0
-        for t, d in zip(self._bk_src[:n], self._bk_dst[:n]):
-            if not (t.is_contiguous() and d.is_contiguous()):
-                return carry, None, 0
-            lo, nb = t.data_ptr(), t.numel() * t.element_size()
-            src = lo
-            for y, x, cn in carry:
-                if lo < x + cn and x < lo + nb:  # overlaps carry destination X
-                    if not (x <= lo and lo + nb <= x + cn):
-                        return carry, None, 0
-                    src = y + (lo - x)
-            bk.append((src, d.data_ptr(), nb))
-        return carry, bk, n
-
-    def _post_prepare(self):
-        """The host half of _post_replay: (span table, fresh output views, non-contiguous rest)."""
-        t = self._post_table()
-        if t["steps_row"] is not None:
-            self._steps_current(t)
-        views, rest = self._clone_alloc(t)
-        return t, views, rest
-
-    def _post_replay(self, prep=None, chain=None, wb: bool = False):
-        """After a replay, in ONE native launch (vmas_copy_spans): the fresh copies of the
-        outputs, the carry of the re-bound state to the next step (Y -> X, which before_actions
-        then skips while no Y changes) and the next step's backups (which backup() then skips
-        while no in-place tensor changes).  The outputs are copied before the carry when one
-        of them lies in a carry destination (two launches).  The span table is built once per
-        (capture, backup buffers): a step only writes its fresh outputs' addresses into it."""
-        t = self._post_table(wb) if prep is None else None
-        if chain is not None and (t is None or t["plain"] or t.get("host") is None):
-            self._launch_chain(chain, wb)  # (a replay's kernel chain not yet launched: now, before anything else)
-            chain = None
-        if t is not None and not t["plain"]:
-            # the common case in one C++ call (csrc/vmas_host.cpp OutputAlloc.post): the replay's
-            # kernel chain (chain: not launched yet), fresh outputs, their addresses into the table,
-            # the launch(es)
-            if t["steps_row"] is not None:
-                self._steps_current(t)
-            host = t.get("host") or self._host_alloc(t)
-            ch = (chain.addr, self._chain_fn(wb)) if chain is not None else (0, 0)
-            mid, hi = (t["n_out"] if t["clash"] else 0), t["n_all"]
-            # (with a deferred launch -- discovery's respawn, whose host side advances the generator
-            # after this -- the draw reads its offset where the respawn launch leaves it)
-            off_dev = self._ahead_offset_word()
-            ahead = (self.env._draw_ahead_plan() if (hi - mid <= 96 and not t["n_bk"] and off_dev is not None)
-                     else None)
-            if ahead is not None:  # (+ the next step's random actions in the same launch)
-                st, drawer, P = ahead
-                # (a single fused launch: these items as its tail, _tail_ok)
-                tail = N.fn_addr("vmas_graph_chain_launch_tail") if ch[0] and not mid and self._tail_ok(t) else 0
-                views, acts, snap, seed, off, inc = N.load_host().post_draw(
-                    host, drawer, mid, hi, P.data_ptr(), P.numel(), N.fn_addr("vmas_copy_spans_draw"), off_dev, *ch,
-                    tail, int(wb))
-                self.env._drew_ahead(st, acts, snap, seed, off, inc)
-            else:
-                views = host.post(mid, hi, *ch)
-            rest = [(views[k], s) for k, s in t["loose"]]
-            self._clone_finish(rest)
-            self._post = {"carry_ver": tuple(map(_VERSION, self._carry_ys)),
-                          "bk_ver": tuple(map(_VERSION, self._inplace)), "bk_n": t["n_bk"]}
-            fn, consts = self._clone_build
-            return fn(views, consts)
-        t, views, rest = prep if prep is not None else self._post_prepare()
-        dev, st = self._dev_index(), self._stream()
-        tbl, n_out, n_all = t["addr"], t["n_out"], t["n_all"]
-        if t["plain"]:  # non-contiguous carries / backups: the old order
-            N.copy_table_at(dev, tbl, 0, n_out, st)
-            t["host"].commit()
-            self._clone_finish(rest)
-            self._post = None
-        else:
-            if t["clash"]:
-                N.copy_table_at(dev, tbl, 0, n_out, st)
-                N.copy_table_at(dev, tbl, n_out, n_all, st)
-            else:
-                N.copy_table_at(dev, tbl, 0, n_all, st)
-            t["host"].commit()
-            self._clone_finish(rest)
-            self._post = {"carry_ver": tuple(map(_VERSION, self._carry_ys)),
-                          "bk_ver": tuple(map(_VERSION, self._inplace)), "bk_n": t["n_bk"]}
-        fn, consts = self._clone_build
-        return fn(views, consts)
-
-    # The post-replay launch's items as the tail of the replay's one fused k_world launch
-    # (csrc/vmas_tail.hpp, vmas_graph_chain_launch_tail): one launch per step instead of two.  A copy
-    # then runs inside the launch that wrote its source, possibly on another XCD, so it is admitted
-    # only when that source is written through: k_world's state outputs (stored sc1) and the
-    # tensors a trusted scenario's program writes through (`_vmas_tail_sources()`: balance's global
-    # shaping, position and ground rewards; transport's per-package distance, on-goal flag, colour and
-    # shaping).  Store words and the step counter need nothing.
-    _TAIL = os.environ.get("VMAS_GRAPH_TAIL", "1") != "0"  # (A/B knob)
-
-    def _tail_ok(self, t) -> bool:
-        ok = t.get("tail_ok")
-        if ok is None:
-            ok = t["tail_ok"] = self._tail_admit(t)
-        return ok
-
-    def _tail_admit(self, t) -> bool:
-        ch, sc = self._chain, self.env.scenario
-        srcs = getattr(sc, "_vmas_tail_sources", None)
-        if (not self._TAIL or ch is None or ch.n_nodes != 1 or not ch.fused or srcs is None or t["plain"]
-                or not _trusted_scenario(sc)):
-            return False
-        ranges = []
-        try:
-            tensors = list(srcs())
-        except Exception:  # noqa: BLE001 -- (an attribute the declaration names is not bound: no tail)
-            return False
-        for v in tensors:
-            if not isinstance(v, Tensor) or not v.is_contiguous() or v.device.type != "cuda":
-                return False
-            ranges.append((v.data_ptr(), v.data_ptr() + v.numel() * v.element_size()))
-        if self._state_idx is not None:  # (the engine's output buffer: k_world's sc1 stores)
-            y = self._carry_src[self._state_idx]
-            ranges.append((y.data_ptr(), y.data_ptr() + y.numel()))
-        for r in t["tbl"]:
-            n, src = int(r["nbytes"]), int(r["src"])
-            if n == N.VMAS_COPY_STORE64 or src == 0 or n == 0:
-                continue
-            if not any(lo <= src and src + n <= hi for lo, hi in ranges):
-                return False
-        return True
-
-    def _post_table(self, wb: bool = False):
-        """The post-replay span table (N.COPY_SPAN_DTYPE rows): the contiguous outputs (their
-        destinations are filled per step by _clone_alloc), then the carry and backup spans."""
-        ts = self._out_tensors
-        if getattr(self, "_clone_src_of", None) is not ts:
-            self._clone_plan()
-            self._clone_src_of = ts
-        cname = "_post_cache_wb" if wb else "_post_cache"  # (a table per variant: with / without the state carry)
-        c = getattr(self, cname, None)  # (objects compared by identity, not id())
-        if (c is not None and c[0] is ts and c[1] is self._bk_dst and c[2] == len(self._bk_dst)
-                and c[3] == len(self._bk_src)):
-            return c[4]
-        out_rows = [(x.data_ptr(), 0, x.numel() * x.element_size()) for _, _, srcs in self._clone_group_srcs
-                    for x in srcs if x.is_contiguous()]
-        direct = self._direct.enabled if self._direct is not None else []
-        direct_rows = []
-        for r in direct:  # (the next replay's buffer offset: written by OutputAlloc.alloc)
-            direct_rows.append(len(out_rows))
-            out_rows.append((0, r["word"], N.VMAS_COPY_STORE64))
-        steps_row = None
-        if self._steps_folded:  # (last output row: the launch of the outputs always covers it)
-            st = self.env.steps
-            steps_row = len(out_rows)
-            out_rows.append((0, st.data_ptr(), st.numel() * 4))
-        carry, bk, n_bk = self._post_spans(wb)
-        plain = bool(self._carry_other) or bk is None
-        extra = [] if plain else carry + bk
-        tbl = np.zeros(len(out_rows) + len(extra), dtype=N.COPY_SPAN_DTYPE)
-        for i, row in enumerate(out_rows + extra):
-            tbl[i] = row
-        clash = any(lo < x + cn and x < lo + nb for lo, _, nb in out_rows if nb > 0 for _, x, cn in carry)
-        t = {"tbl": tbl, "addr": tbl.ctypes.data, "n_out": len(out_rows), "n_all": len(out_rows) + len(extra),
-             "plain": plain,
-             "clash": clash, "n_bk": n_bk, "steps_row": steps_row, "steps": self.env.steps if self._steps_folded else None,
-             "direct_rows": direct_rows,
-             "contig": [[x.is_contiguous() for x in srcs] for _, _, srcs in self._clone_group_srcs]}
-        setattr(self, cname, (ts, self._bk_dst, len(self._bk_dst), len(self._bk_src), t))
-        return t
-
-    def _steps_current(self, t) -> None:
-        """Point the table's increment row at env.steps as bound now (reset() re-binds it)."""
-        st = self.env.steps  # (checked by before_actions: fp32, contiguous, on the device)
-        if t["steps"] is not st:
-            t["tbl"][t["steps_row"]]["dst"] = st.data_ptr()
-            t["tbl"][t["steps_row"]]["nbytes"] = st.numel() * 4
-            t["steps"] = st
-
-    def _host_alloc(self, t):
-        """The table's OutputAlloc (csrc/vmas_host.cpp): per (dtype, shape) group one allocation
-        split into its members, the contiguous members' addresses into the table's output rows."""
-        groups, row, loose, start = [], 0, [], 0
-        for (dt, shape, n), (_, _, srcs), contig in zip(self._clone_groups, self._clone_group_srcs, t["contig"]):
-            ks = [k for k, c in enumerate(contig) if c]
-            groups.append((srcs[0], list(shape), n, row, ks))
-            loose += [(start + k, srcs[k]) for k, c in enumerate(contig) if not c]
-            row += len(ks)
-            start += n
-        direct = self._direct.enabled if self._direct is not None else []
-        regions = [(r["buf"], r["box"], r["members"][0], row,
-                    [(list(m.shape), list(m.stride()), m.storage_offset()) for m in r["members"]])
-                   for r, row in zip(direct, t["direct_rows"])]
-        host = N.load_host().OutputAlloc(self._dev_index(), groups, t["tbl"], t["addr"], N.fn_addr("vmas_copy_spans"),
-                                         N.fn_addr("vmas_aux_last_error"), regions)
-        t["host"], t["loose"] = host, loose
-        return host
-
-    def _clone_alloc(self, t):
-        """Fresh output tensors for one step, their addresses written into the table's output
-        rows: (views in the plan's order, the non-contiguous (dst, src) rest)."""
-        host = t.get("host") or self._host_alloc(t)
-        views = host.alloc()
-        return views, [(views[k], s) for k, s in t["loose"]]
-
-    def _clone_alloc_py(self, t):
-        """_clone_alloc in Python (kept as the statement of what OutputAlloc.alloc does)."""
-        plan = t.get("alloc")
-        if plan is None:  # per table: each group's rows and the byte offsets of its contiguous members
-            plan, row = [], 0
-            dev = self._out_tensors[0].device
-            for (dt, shape, n), (_, _, srcs), contig in zip(self._clone_groups, self._clone_group_srcs, t["contig"]):
-                step = int(np.prod(shape, dtype=np.int64)) * torch.empty((), dtype=dt).element_size()
-                ks = [k for k, c in enumerate(contig) if c]
-                plan.append(((n,) + shape, dt, dev, row, row + len(ks), np.array(ks, dtype=np.uint64) * np.uint64(step),
-                             [(k, srcs[k]) for k, c in enumerate(contig) if not c]))
-                row += len(ks)
-            t["alloc"] = plan
-        views = ()
-        dst = t["tbl"]["dst"]
-        rest = []
-        for shape, dt, dev, r0, r1, offs, loose in plan:
-            buf = torch.empty(shape, dtype=dt, device=dev)
-            vs = buf.unbind(0)
-            views += vs
-            if r1 > r0:
-                np.add(offs, buf.data_ptr(), out=dst[r0:r1], casting="unsafe")
-            for k, src in loose:
-                rest.append((vs[k], src))
-        return views, rest
-
-    def _clone_plan(self):
-        """Outputs grouped by (dtype, shape): per group one allocation [n, *shape] whose unbind
-        gives the n fresh tensors, all filled by the post-replay copy launch; the result tree rebuilt by a
-        function generated for its structure.  Built once per capture (the replay's output tensors
-        are fixed), so a step makes a handful of host calls instead of several per output."""
-        ts = self._out_tensors
-        direct = self._direct.enabled if self._direct is not None else []
-        dmember = {id(m): (ri, mi) for ri, r in enumerate(direct) for mi, m in enumerate(r["members"])}
-        groups: Dict[Tuple[torch.dtype, Tuple[int, ...]], List[int]] = {}
-        for i, t in enumerate(ts):
-            if id(t) not in dmember:  # (directly written: views of the replay's fresh buffer)
-                groups.setdefault((t.dtype, tuple(t.shape)), []).append(i)
-        plan = sorted(groups.items(), key=lambda kv: str(kv[0][0]))  # same dtypes adjacent
-        self._clone_groups = [(dt, shape, len(idx)) for (dt, shape), idx in plan]
-        order = [i for _, idx in plan for i in idx]  # position in the concatenated views -> output
-        pos = {i: p for p, i in enumerate(order)}
-        # the direct categories' members follow the groups' views (OutputAlloc.alloc's order)
-        base, at = [], len(order)
-        for r in direct:
-            base.append(at)
-            at += len(r["members"])
-        for i, t in enumerate(ts):
-            if id(t) in dmember:
-                ri, mi = dmember[id(t)]
-                pos[i] = base[ri] + mi
-        # per (dtype, shape) group, in view order: its sources
-        self._clone_group_srcs, start = [], 0
-        for _, idx in plan:
-            self._clone_group_srcs.append((start, start + len(idx), [ts[i] for i in idx]))
-            start += len(idx)
-        consts: List[Any] = []
-        counter = [0]
-
-        def expr(t):
-            if isinstance(t, Tensor):
-                counter[0] += 1
-                return f"v[{pos[counter[0] - 1]}]"
-            if isinstance(t, list):
-                return "[" + ", ".join(expr(x) for x in t) + "]"
-            if isinstance(t, tuple):
-                return "(" + "".join(expr(x) + ", " for x in t) + ")"
-            if isinstance(t, dict):
-                items = []
-                for k, x in t.items():
-                    consts.append(k)
-                    items.append(f"c[{len(consts) - 1}]: {expr(x)}")
-                return "{" + ", ".join(items) + "}"
-            consts.append(t)
-            return f"c[{len(consts) - 1}]"
-
-        body = expr(self._out_tree)
-        fn = eval("lambda v, c: " + body)  # noqa: S307 -- generated from the output tree's structure only
-        self._clone_build = (fn, consts)
-
-    @staticmethod
-    def _clone_finish(rest):
-        for v, t in rest:
-            v.copy_(t)
-
-    def _clone_outputs(self):
-        """Fresh copies of the replay's outputs (the reference returns fresh tensors too)."""
-        t = self._post_table()
-        if t["steps_row"] is not None:
-            self._steps_current(t)
-        views, rest = self._clone_alloc(t)
-        N.copy_table_at(self._dev_index(), t["addr"], 0, t["n_out"], self._stream())
-        t["host"].commit()
-        self._clone_finish(rest)
-        fn, consts = self._clone_build
-        return fn(views, consts)
+    # the post-replay launch's items as the tail of the replay's one fused k_world launch
+    # (PostStage._tail_admit); 0: a launch of its own (A/B knob)
+    _TAIL = os.environ.get("VMAS_GRAPH_TAIL", "1") != "0"
