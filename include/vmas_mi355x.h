@@ -47,8 +47,9 @@ extern "C" {
  * v7: VmasDiscreteActionRef, vmas_apply_discrete_actions / _launch
  * v8: VmasRenderPrim / VmasRenderEntity / VmasRenderLidar / VmasRenderScene, vmas_render_frames,
  *     vmas_render_scene
- * v9: VmasMaskedSpan / vmas_masked_rows, VmasBalanceResetIO / vmas_balance_reset */
-#define VMAS_ABI_VERSION 9
+ * v9: VmasMaskedSpan / vmas_masked_rows, VmasBalanceResetIO / vmas_balance_reset
+ * v10: VmasNavigationIO / vmas_navigation_outputs */
+#define VMAS_ABI_VERSION 10
 
 /* error codes */
 #define VMAS_OK 0
@@ -651,6 +652,64 @@ int32_t vmas_flocking_outputs(int32_t device, const VmasFlockingIO* io, void* st
  * tensor / Python-scalar division (t * f32(1 / period)). */
 int32_t vmas_flocking_target_action(int32_t device, const float* t, int32_t batch, float period, float* u,
                                     void* stream);
+
+/* navigation (reference vmas/scenarios/navigation.py:199-277): replaces, for every agent at once,
+ * Scenario.reward (the first agent's block: per agent distance_to_goal, on_goal, pos_rew and the
+ * re-bound pos_shaping; the shared pos_rew summed from zero in agent order, all_goal_reached,
+ * final_rew, the pairwise collision penalties over the pairs (i, j < i); then every agent's
+ * (pos + final_rew) + agent_collision_rew), Scenario.observation (pos, vel, pos - goal for the own
+ * goal or every agent's, max_range - LIDAR; the LIDAR sees the other agents) and Scenario.done.
+ * Sphere agents only (checked; the scenario keeps its torch program otherwise).
+ * The reference adds a pair's penalty only where World.collides(a, b) holds, whose last test is
+ * batch-wide (any env with |pa - pb| <= the circumscribed radii).  The REWARD launch applies the
+ * static part (pair_static) per env and collects the batch-wide flags in `ws`; a one-workgroup
+ * launch behind it (k_navigation_pairs; none when pair_static is all zero) reads them and, where a
+ * pair was near in some env and touching in none, rewrites the collision rewards and the rewards
+ * without that pair -- the reference's values in every case.  `ws`: VMAS_NAV_WS_WORDS zeroed 32-bit
+ * device words owned by the caller, zero again when the call's launches end.
+ * Grid: the exact form one thread per (env, agent, part) as flocking; the fast form a wave per
+ * (64 envs, agent). */
+#define VMAS_NAV_MAX_AGENTS 16 /* the struct travels as kernel arguments (< 4 KiB) */
+#define VMAS_NAV_WS_WORDS 32
+typedef struct VmasNavigationIO {
+    int32_t batch, n_agents, what, n_rays;
+    int32_t shared_rew, observe_all_goals;
+    int32_t lidar_on;                      /* collisions: every agent has its LIDAR (the other agents) */
+    int32_t fast_lidar;                    /* 1: a wave per (64 envs, agent), direct ray-sphere form
+                                              (k_navigation_fast; LIDAR within the parity tolerance);
+                                              0: bit-identical to k_cast_rays */
+    float pos_shaping_factor, final_reward, agent_collision_penalty, min_collision_distance;
+    float max_range, pad0;
+    VmasShapeRef agents[VMAS_NAV_MAX_AGENTS]; /* world.agents, in order (spheres) */
+    VmasVec goal_pos[VMAS_NAV_MAX_AGENTS];    /* [B,2] agent.goal.state.pos */
+    float goal_radius[VMAS_NAV_MAX_AGENTS];   /* agent.goal.shape.radius (on_goal) */
+    double circ[VMAS_NAV_MAX_AGENTS];         /* shape.circumscribed_radius(), summed per pair in double
+                                                 as World.collides does before the f32 comparison */
+    uint32_t pair_static[VMAS_NAV_MAX_AGENTS]; /* bit j (< i) of [i]: the static part of
+                                                  World.collides(agents[i], agents[j]) */
+    VmasVec vel[VMAS_NAV_MAX_AGENTS];         /* [B,2] (OBS) */
+    VmasVec rot[VMAS_NAV_MAX_AGENTS];         /* [B,1]: the LIDAR's angle offset (OBS, lidar_on) */
+    const float* angles[VMAS_NAV_MAX_AGENTS]; /* [B, n_rays] (Lidar._angles) */
+    int32_t ang_s0[VMAS_NAV_MAX_AGENTS], ang_s1[VMAS_NAV_MAX_AGENTS];
+    const float* shaping_in[VMAS_NAV_MAX_AGENTS]; /* [B] contiguous: agent.pos_shaping (REWARD) */
+    float* shaping_out[VMAS_NAV_MAX_AGENTS];      /* [B] fresh */
+    float* dist_to_goal[VMAS_NAV_MAX_AGENTS];     /* [B] fresh */
+    uint8_t* on_goal[VMAS_NAV_MAX_AGENTS];        /* [B] torch.bool fresh */
+    float* agent_pos_rew[VMAS_NAV_MAX_AGENTS];    /* [B] fresh */
+    float* collision_rew[VMAS_NAV_MAX_AGENTS];    /* [B] in place */
+    float* rewards[VMAS_NAV_MAX_AGENTS];          /* [B] fresh */
+    float* obs[VMAS_NAV_MAX_AGENTS];              /* [B, 4 + 2 goals + n_rays] fresh (OBS) */
+    float* lidar[VMAS_NAV_MAX_AGENTS];            /* [B, n_rays] fresh (OBS): Lidar._last_measurement */
+    float* pos_rew;                               /* [B] in place (REWARD): the shared pos_rew */
+    float* final_rew;                             /* [B] in place */
+    uint8_t* all_goal_reached;                    /* [B] torch.bool fresh */
+    uint8_t* done;                                /* [B] torch.bool (DONE) */
+    uint32_t* ws;                                 /* VMAS_NAV_WS_WORDS words (REWARD), see above */
+    const int64_t* out_delta;            /* optional (graph mode's direct outputs): three device words,
+                                             the byte offsets added to the obs / rewards / done pointers
+                                             (simulator/environment/_graph.py DirectOutputs); NULL: none */
+} VmasNavigationIO;
+int32_t vmas_navigation_outputs(int32_t device, const VmasNavigationIO* io, void* stream);
 
 /* transport (reference vmas/scenarios/transport.py:130-190): replaces Scenario.reward (for the
  * first agent: per package dist_to_goal, on_goal = is_overlapping(package, goal), the colour,

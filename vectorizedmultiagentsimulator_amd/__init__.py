@@ -14,8 +14,8 @@ def render_interactively(*args, **kwargs):
     raise NotImplementedError("interactive rendering is not part of the MI355X engine")
 
 
-scenarios = sorted(["balance", "transport", "discovery", "flocking"])
-"""Benchmark scenarios restated for the engine."""
+scenarios = sorted(["balance", "transport", "discovery", "flocking", "navigation"])
+"""Scenarios restated for the engine, each with a fused native per-step program."""
 
 debug_scenarios = sorted(["pollock", "waterfall"])
 """Parity fixtures (all shape pairs; joints)."""

@@ -19,7 +19,7 @@ LIB_PATH = Path(os.environ.get("VMAS_LIB_PATH") or Path(__file__).resolve().pare
 
 # ------------------------------------------------------------------------------------------------
 # constants mirrored from include/vmas_mi355x.h
-VMAS_ABI_VERSION = 9
+VMAS_ABI_VERSION = 10
 VMAS_SPHERE, VMAS_BOX, VMAS_LINE = 0, 1, 2
 (
     VMAS_PAIR_JOINT,
@@ -83,6 +83,7 @@ EXPORTED_SYMBOLS = (
     "vmas_cast_rays_vjp",
     "vmas_flocking_outputs",
     "vmas_flocking_target_action",
+    "vmas_navigation_outputs",
     "vmas_assert_publish_range",
     "vmas_transport_outputs",
     "vmas_discovery_outputs",
@@ -490,6 +491,29 @@ class VmasFlockingIO(ctypes.Structure):
     ]
 
 
+VMAS_NAV_MAX_AGENTS = 16
+VMAS_NAV_WS_WORDS = 32
+_NA = VMAS_NAV_MAX_AGENTS
+
+
+class VmasNavigationIO(ctypes.Structure):
+    _fields_ = [
+        ("batch", _i32), ("n_agents", _i32), ("what", _i32), ("n_rays", _i32),
+        ("shared_rew", _i32), ("observe_all_goals", _i32), ("lidar_on", _i32), ("fast_lidar", _i32),
+        ("pos_shaping_factor", _f32), ("final_reward", _f32), ("agent_collision_penalty", _f32),
+        ("min_collision_distance", _f32), ("max_range", _f32), ("pad0", _f32),
+        ("agents", VmasShapeRef * _NA), ("goal_pos", VmasVec * _NA), ("goal_radius", _f32 * _NA),
+        ("circ", ctypes.c_double * _NA), ("pair_static", _u32 * _NA),
+        ("vel", VmasVec * _NA), ("rot", VmasVec * _NA), ("angles", _vp * _NA),
+        ("ang_s0", _i32 * _NA), ("ang_s1", _i32 * _NA),
+        ("shaping_in", _vp * _NA), ("shaping_out", _vp * _NA), ("dist_to_goal", _vp * _NA), ("on_goal", _vp * _NA),
+        ("agent_pos_rew", _vp * _NA), ("collision_rew", _vp * _NA), ("rewards", _vp * _NA), ("obs", _vp * _NA),
+        ("lidar", _vp * _NA),
+        ("pos_rew", _vp), ("final_rew", _vp), ("all_goal_reached", _vp), ("done", _vp), ("ws", _vp),
+        ("out_delta", _vp),  # (graph mode's direct outputs: [obs, rewards, done] byte offsets)
+    ]
+
+
 VMAS_TRANSPORT_MAX_PACKAGES = 8
 VMAS_TRANSPORT_MAX_AGENTS = 16
 _TP, _TA = VMAS_TRANSPORT_MAX_PACKAGES, VMAS_TRANSPORT_MAX_AGENTS
@@ -672,6 +696,8 @@ def load_library(path: os.PathLike | str | None = None) -> ctypes.CDLL:
     lib.vmas_transport_outputs.argtypes = [_i32, _vp, _vp]
     lib.vmas_flocking_outputs.restype = _i32
     lib.vmas_flocking_outputs.argtypes = [_i32, _vp, _vp]
+    lib.vmas_navigation_outputs.restype = _i32
+    lib.vmas_navigation_outputs.argtypes = [_i32, _vp, _vp]
     lib.vmas_distance_vjp.restype = _i32
     lib.vmas_distance_vjp.argtypes = [_i32, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
     lib.vmas_cast_rays_vjp.restype = _i32

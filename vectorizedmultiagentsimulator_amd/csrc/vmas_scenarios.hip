@@ -329,6 +329,418 @@ __global__ void __launch_bounds__(256) k_flocking_fast(VmasFlockingIO io_arg) {
     }
 }
 
+// ---- navigation (navigation.py:199-277; restated in scenarios/navigation.py) -----------------------
+// The reward block of agent k in env b is computed by the wave of (64 envs, k): every agent's
+// distance to its goal (the shared pos_rew is their sum from zero in agent order, all_goal_reached
+// their conjunction: each wave recomputes them rather than meeting in LDS -- n norms against a
+// LIDAR's rays x targets), k's own outputs, and k's collision reward over the pairs it is part of.
+// NA: the static bound of the agent loops (the agent count in the unrolled instantiations).
+constexpr int kNavMA = VMAS_NAV_MAX_AGENTS;
+// ws words: [0, 16) word i bit j (< i): the pair (i, j) touches in some env (World.collides' last
+// test), [16, 32) it is near (distance <= min_collision_distance) in some env
+constexpr int kNavWsNear = 16;
+static_assert(2 * kNavMA <= VMAS_NAV_WS_WORDS && kNavMA <= 16, "navigation scratch words");
+
+template <int NA, class IO>
+__device__ __forceinline__ void nav_load(IO& io, int bb, V2* P, V2* G) {
+    const int n = io.n_agents;
+#pragma unroll
+    for (int j = 0; j < NA; ++j) {
+        const VmasShapeRef aj = io.agents[j];
+        const VmasVec gj = io.goal_pos[j];
+        P[j] = j < n ? ref_pos(aj, bb) : mk(0.f, 0.f);
+        G[j] = j < n ? ld_vec2(gj, bb) : mk(0.f, 0.f);
+    }
+}
+template <int NA>
+__device__ __forceinline__ V2 nav_sel(const V2* P, int k) {  // P[k] with static register indices
+    V2 r = mk(0.f, 0.f);
+#pragma unroll
+    for (int j = 0; j < NA; ++j)
+        if (j == k) r = P[j];
+    return r;
+}
+// done(): every agent within its OWN radius of its goal (on_goal compares with the goal's)
+template <int NA, class IO>
+__device__ __forceinline__ bool nav_done(IO& io, const V2* P, const V2* G) {
+    bool all = true;
+#pragma unroll
+    for (int j = 0; j < NA; ++j)
+        if (j < io.n_agents) all = all && (xnorm(P[j] - G[j]) < io.agents[j].radius);
+    return all;
+}
+// agent k's collision reward: a.agent_collision_rew[:] = 0, then the penalty once per pair (hi, lo <
+// hi) that k is part of, World.collides(hi, lo) holds for (its static part; the batch-wide part:
+// nav_pairs) and get_distance(hi, lo) = (|p_hi - p_lo| - r_hi) - r_lo
+// <= min_collision_distance.  (Every addend is the same constant: the sum depends on their number
+// only, not on the pairs' order.)  touch / near: the flags of the pairs (k, j < k) in this env.
+template <int NA, class IO>
+__device__ __forceinline__ float nav_collision(IO& io, const V2* P, V2 pk, int k, uint32_t* touch, uint32_t* near) {
+    const int n = io.n_agents;
+    const float radk = io.agents[k].radius;
+    const uint32_t stk = io.pair_static[k];
+    const double ck = io.circ[k];
+    float cr = 0.f;
+    uint32_t tb = 0u, nb = 0u;
+#pragma unroll
+    for (int j = 0; j < NA; ++j) {
+        if (j >= n || j == k) continue;
+        const bool lower = j < k;
+        if (!((lower ? (stk >> j) : (io.pair_static[j] >> k)) & 1u)) continue;
+        const float radj = io.agents[j].radius;
+        const V2 ph = lower ? pk : P[j], pl = lower ? P[j] : pk;
+        const float nrm = xnorm(ph - pl);
+        const float d = (nrm - (lower ? radk : radj)) - (lower ? radj : radk);
+        const bool nr = d <= io.min_collision_distance;
+        if (nr) cr = cr + io.agent_collision_penalty;
+        if (lower) {
+            tb |= (nrm <= (float)(ck + io.circ[j])) ? (1u << j) : 0u;
+            nb |= nr ? (1u << j) : 0u;
+        }
+    }
+    *touch = tb;
+    *near = nb;
+    return cr;
+}
+
+// The batch-wide part of World.collides, after a REWARD launch (k_navigation_pairs, one workgroup):
+// a pair near in some env and touching in none was penalised per env above but the reference skips
+// it -- then (rare) the collision rewards and rewards of every env again, with the pairs that touch
+// somewhere.  Leaves ws zero.  (A launch of its own: the kernel boundary orders it after every
+// wave's outputs and flags.  Done by the last wave of the REWARD launch itself -- an agent-scope
+// fence and a counter increment per wave -- that launch took 56 us at 32 768 envs x 4 agents and
+// 107 us x 8, the waves queueing on the counter.)
+template <class IO>
+__device__ __forceinline__ void nav_pairs(IO& io, const OutDelta& od, int tid, int nthreads, uint32_t* EN) {
+    const int n = io.n_agents;
+    bool need = false;
+    for (int i = 0; i < n; ++i) {
+        const uint32_t t = io.ws[i], nr = io.ws[kNavWsNear + i];
+        if (tid == 0) EN[i] = t;
+        need = need || (nr & ~t) != 0u;
+    }
+    __syncthreads();
+    if (tid < 2 * kNavMA) io.ws[tid] = 0u;
+    if (!need) return;
+    // (rolled: positions from memory per pair, nav_collision's operations)
+    for (int b = tid; b < io.batch; b += nthreads) {
+        const float s = io.pos_rew[b], fin = io.final_rew[b];
+#pragma unroll 1
+        for (int k = 0; k < n; ++k) {
+            const VmasShapeRef ak = io.agents[k];
+            const V2 pk = ref_pos(ak, b);
+            float cr = 0.f;
+#pragma unroll 1
+            for (int j = 0; j < n; ++j) {
+                const int hi = j < k ? k : j, lo = j < k ? j : k;
+                if (j == k || !((io.pair_static[hi] >> lo) & (EN[hi] >> lo) & 1u)) continue;
+                const VmasShapeRef aj = io.agents[j];
+                const V2 pj = ref_pos(aj, b);
+                const float nrm = xnorm(j < k ? pk - pj : pj - pk);
+                const float d = (nrm - (j < k ? ak.radius : aj.radius)) - (j < k ? aj.radius : ak.radius);
+                if (d <= io.min_collision_distance) cr = cr + io.agent_collision_penalty;
+            }
+            io.collision_rew[k][b] = cr;
+            moved(io.rewards[k], od.rew)[b] = ((io.shared_rew ? s : io.agent_pos_rew[k][b]) + fin) + cr;
+        }
+    }
+}
+
+// REWARD (and DONE with it) of agent k for the wave's 64 envs; every lane of the wave calls.
+template <int NA, class IO>
+__device__ __forceinline__ void nav_reward(IO& io, int b, bool valid, int k, int lane, const OutDelta& od, const V2* P,
+                                           const V2* G) {
+    const int n = io.n_agents;
+    // self.pos_rew[:] = 0; for a in agents: self.pos_rew += agent_reward(a)
+    float s = 0.f, dk = 0.f, shk = 0.f, rk = 0.f;
+    bool all = true, onk = false;
+    const int bb = valid ? b : io.batch - 1;
+#pragma unroll
+    for (int j = 0; j < NA; ++j) {
+        if (j >= n) continue;
+        const float dist = xnorm(P[j] - G[j]);  // distance_to_goal
+        const bool on = dist < io.goal_radius[j];
+        const float shaping = dist * io.pos_shaping_factor;
+        const float pr = io.shaping_in[j][bb] - shaping;
+        s = s + pr;
+        all = all && on;
+        if (j == k) {
+            dk = dist;
+            shk = shaping;
+            rk = pr;
+            onk = on;
+        }
+    }
+    const float fin = all ? io.final_reward : 0.f;  // final_rew[:] = 0; final_rew[all_goal_reached] = final_reward
+    uint32_t tb, nb;
+    const float cr = nav_collision<NA>(io, P, nav_sel<NA>(P, k), k, &tb, &nb);
+    if (valid) {
+        io.dist_to_goal[k][b] = dk;
+        io.on_goal[k][b] = onk ? 1 : 0;
+        io.shaping_out[k][b] = shk;
+        io.agent_pos_rew[k][b] = rk;
+        io.collision_rew[k][b] = cr;
+        moved(io.rewards[k], od.rew)[b] = ((io.shared_rew ? s : rk) + fin) + cr;  // (pos + final_rew) + collision
+        if (k == 0) {
+            io.pos_rew[b] = s;
+            io.final_rew[b] = fin;
+            io.all_goal_reached[b] = all ? 1 : 0;
+            if (io.what & VMAS_SCN_DONE) moved(io.done, od.done)[b] = nav_done<NA>(io, P, G) ? 1 : 0;
+        }
+    } else {
+        tb = nb = 0u;
+    }
+    // the wave's pair flags for k_navigation_pairs (no lane near: no atomic)
+    if (__ballot((tb | nb) != 0u) != 0ull) {
+        uint32_t wt = 0u, wn = 0u;
+#pragma unroll
+        for (int j = 0; j < kNavMA; ++j) {
+            wt |= __ballot((tb >> j) & 1u) != 0ull ? (1u << j) : 0u;
+            wn |= __ballot((nb >> j) & 1u) != 0ull ? (1u << j) : 0u;
+        }
+        if (lane == 0) {
+            if (wt) atomicOr(io.ws + k, wt);
+            if (wn) atomicOr(io.ws + kNavWsNear + k, wn);
+        }
+    }
+}
+
+// the head of agent k's observation row: pos, vel, pos - goal (own, or every agent's)
+template <int NA, class IO>
+__device__ __forceinline__ void nav_head(IO& io, int bb, int k, const V2* P, const V2* G, float* o) {
+    const V2 pk = nav_sel<NA>(P, k);
+    const VmasVec vv = io.vel[k];
+    const V2 v = ld_vec2(vv, bb);
+    o[0] = pk.x;
+    o[1] = pk.y;
+    o[2] = v.x;
+    o[3] = v.y;
+    if (io.observe_all_goals) {
+#pragma unroll
+        for (int j = 0; j < NA; ++j)
+            if (j < io.n_agents) {
+                o[4 + 2 * j] = pk.x - G[j].x;
+                o[5 + 2 * j] = pk.y - G[j].y;
+            }
+    } else {
+        const V2 g = nav_sel<NA>(G, k);
+        o[4] = pk.x - g.x;
+        o[5] = pk.y - g.y;
+    }
+}
+
+#ifdef __HIP_DEVICE_COMPILE__
+typedef const VmasNavigationIO __attribute__((address_space(4))) KNavigationIO;  // (see k_flocking_fast)
+#else
+typedef const VmasNavigationIO KNavigationIO;
+#endif
+
+// The program with the LIDAR bit-identical to k_cast_rays (io.fast_lidar == 0, or a shape over the
+// fast form's caps).  Grid as k_flocking: x = 64-env groups, y = (agent k, part): part 0 is k's
+// reward, done (k == 0) and the observation head, part 1 + r is ray r of k's LIDAR over the other
+// agents in order.
+__global__ void __launch_bounds__(64) k_navigation(VmasNavigationIO io_arg) {
+    constexpr int MA = kNavMA;
+#ifdef __HIP_DEVICE_COMPILE__
+    KNavigationIO& io = *(KNavigationIO*)__builtin_amdgcn_kernarg_segment_ptr();
+    (void)io_arg;
+#else
+    KNavigationIO& io = io_arg;
+#endif
+    const int lane = (int)threadIdx.x, b = (int)blockIdx.x * 64 + lane;
+    const bool valid = b < io.batch;
+    const int bb = valid ? b : io.batch - 1;
+    const int nr = io.lidar_on ? io.n_rays : 0;
+    const int parts = (io.what & VMAS_SCN_OBS) ? 1 + nr : 1;
+    const int k = __builtin_amdgcn_readfirstlane((int)blockIdx.y / parts);
+    const int part = (int)blockIdx.y - k * parts;
+    const int H = 4 + 2 * (io.observe_all_goals ? io.n_agents : 1), W = H + nr;
+    const OutDelta od = load_out_delta(io);
+    V2 P[MA], G[MA];
+    nav_load<MA>(io, bb, P, G);
+    if (part == 0) {
+        if ((io.what & VMAS_SCN_OBS) && valid) nav_head<MA>(io, b, k, P, G, moved(io.obs[k], od.obs) + (long)b * W);
+        if (io.what & VMAS_SCN_REWARD) nav_reward<MA>(io, b, valid, k, lane, od, P, G);
+        else if ((io.what & VMAS_SCN_DONE) && k == 0 && valid) moved(io.done, od.done)[b] = nav_done<MA>(io, P, G) ? 1 : 0;
+        return;
+    }
+    if (!valid) return;
+    // LIDAR ray r: Lidar.measure = World.cast_rays(angles + agent rot) (cast_one)
+    const int r = part - 1;
+    const V2 pk = nav_sel<MA>(P, k);
+    const VmasVec rv = io.rot[k];
+    const float a = io.angles[k][(long)b * io.ang_s0[k] + (long)r * io.ang_s1[k]] + ld_vec1(rv, b);
+    const float dc = cosf(a), ds = sinf(a);
+    float best = io.max_range;
+#pragma unroll
+    for (int j = 0; j < MA; ++j)
+        if (j < io.n_agents && j != k) best = tmin(best, ray_sphere(pk, dc, ds, P[j], io.agents[j].radius, io.max_range));
+    io.lidar[k][(long)b * nr + r] = best;
+    moved(io.obs[k], od.obs)[(long)b * W + H + r] = io.max_range - best;
+}
+
+__global__ void __launch_bounds__(1024) k_navigation_pairs(VmasNavigationIO io_arg) {
+#ifdef __HIP_DEVICE_COMPILE__
+    KNavigationIO& io = *(KNavigationIO*)__builtin_amdgcn_kernarg_segment_ptr();
+    (void)io_arg;
+#else
+    KNavigationIO& io = io_arg;
+#endif
+    __shared__ uint32_t EN[kNavMA];
+    nav_pairs(io, load_out_delta(io), (int)threadIdx.x, (int)blockDim.x, EN);
+}
+
+// The fast LIDAR's ray direction and ray-sphere distance.  k_flocking_fast's pair (hardware sin /
+// cos, ray_sphere_fast_nan) was measured first and missed the LIDAR parity condition here: at
+// navigation's geometry (centres up to 0.45 from the origin, radius 0.1, positions of magnitude 1)
+// the direct form's r^2 - dn^2 = t^2 + (r^2 - |u|^2) cancels to ~5e-8 in `a`, and the hardware
+// instructions turn the ray by up to ~3e-7 rad (another ~3e-8 in `a`); a grazing hit (a ~ 1e-7)
+// then lands 6.7e-5 from the oracle, beyond what a certification turn reproduces (2 of 16 384 rows
+// at 4 096 envs).  So: dn as the cross product u x dir (no cancellation: ~6e-9 in `a`), and the
+// direction from a Cody-Waite reduction by pi / 2 with the Cephes sinf / cosf polynomials (angle
+// error <= 1e-7 rad against double precision over +-16 rad, ~20 VALU a ray), ocml's sincosf beyond
+// kFastTrigMaxAngle.  NaN on a miss, dropped by min_drop_nan, as ray_sphere_fast_nan.
+__device__ __forceinline__ void nav_sincos(float x, float& s, float& c) {
+    if (!(fabsf(x) < kFastTrigMaxAngle)) {
+        sincosf(x, &s, &c);
+        return;
+    }
+    const float k = rintf(x * 0.636619772f);  // 2 / pi
+    float r = __builtin_fmaf(-k, 1.5703125f, x);  // pi / 2 in three parts; the first product is exact
+    r = __builtin_fmaf(-k, 4.837512969970703125e-4f, r);
+    r = __builtin_fmaf(-k, 7.54978995489188216e-8f, r);
+    const float z = r * r;
+    float ps = __builtin_fmaf(-1.9515295891e-4f, z, 8.3321608736e-3f);
+    ps = __builtin_fmaf(ps, z, -1.6666654611e-1f);
+    const float sr = __builtin_fmaf(r * z, ps, r);
+    float pc = __builtin_fmaf(2.443315711809948e-5f, z, -1.388731625493765e-3f);
+    pc = __builtin_fmaf(pc, z, 4.166664568298827e-2f);
+    const float cr = __builtin_fmaf(z * z, pc, __builtin_fmaf(-0.5f, z, 1.0f));
+    const int q = (int)k & 3;
+    const float a = (q & 1) ? cr : sr, b = (q & 1) ? sr : cr;
+    s = (q & 2) ? -a : a;
+    c = ((q + 1) & 2) ? -b : b;
+}
+__device__ __forceinline__ float nav_ray_nan(float ux, float uy, float r2, float dc, float ds) {
+    const float t = __builtin_fmaf(ux, dc, uy * ds);      // the foot point's distance along the ray
+    const float dn = __builtin_fmaf(ux, ds, -(uy * dc));  // the centre's distance from the ray's line
+    const float a = __builtin_fmaf(-dn, dn, r2);
+    return t - __builtin_amdgcn_sqrtf(__builtin_fminf(a, t * 1e30f));
+}
+
+// The same program with the fast LIDAR (io.fast_lidar, the default), laid out as k_flocking_fast:
+// grid x = 64-env groups, y = groups of 4 agents; a wave per (64 envs, agent): its reward, its
+// observation head and all of its rays (angles, positions and goals loaded up front; nav_sincos /
+// nav_ray_nan above), the rows staged in LDS (4 x 64 x W floats, sized by the launch) and written
+// out as contiguous blocks.  NR / NT > 0: the ray and target counts fixed at compile time (12
+// rays; 1..7 targets, i.e. 2..8 agents), every ray unrolled; otherwise the rolled runtime form.
+// The LIDAR's targets are the other agents in order.
+constexpr int kNavFastRays = 16, kNavFastTargets = kNavMA - 1;
+template <int NR, int NT>
+__global__ void __launch_bounds__(256) k_navigation_fast(VmasNavigationIO io_arg) {
+    constexpr int RM = NR > 0 ? NR : kNavFastRays, TM = NT > 0 ? NT : kNavFastTargets;
+    constexpr int NA = NT > 0 ? NT + 1 : kNavMA;
+#ifdef __HIP_DEVICE_COMPILE__
+    KNavigationIO& io = *(KNavigationIO*)__builtin_amdgcn_kernarg_segment_ptr();
+    (void)io_arg;
+#else
+    KNavigationIO& io = io_arg;
+#endif
+    extern __shared__ float nav_lds[];
+    const int lane = (int)(threadIdx.x & 63u), w = (int)(threadIdx.x >> 6);
+    const int g0 = (int)blockIdx.x * 64, b = g0 + lane;
+    const int k = __builtin_amdgcn_readfirstlane((int)blockIdx.y * 4 + w);
+    const int n = io.n_agents;
+    if (k >= n) return;  // (wave-uniform; no workgroup barrier below)
+    const bool valid = b < io.batch;
+    const int bb = valid ? b : io.batch - 1;
+    const int nr = NR > 0 ? NR : (io.lidar_on ? io.n_rays : 0), nt = NT > 0 ? NT : n - 1;
+    const int H = 4 + 2 * (io.observe_all_goals ? n : 1), W = H + nr;
+    float* S = nav_lds + w * 64 * W;
+    const int row = lane * W;
+    const OutDelta od = load_out_delta(io);
+    V2 P[NA], G[NA];
+    if (!(io.what & VMAS_SCN_OBS)) {
+        nav_load<NA>(io, bb, P, G);
+        if (io.what & VMAS_SCN_REWARD) nav_reward<NA>(io, b, valid, k, lane, od, P, G);
+        else if ((io.what & VMAS_SCN_DONE) && k == 0 && valid) moved(io.done, od.done)[b] = nav_done<NA>(io, P, G) ? 1 : 0;
+        return;
+    }
+    // loads first (independent): angles, rotation, positions, goals
+    float A[RM];
+    float rot = 0.f;
+    if (nr > 0) {
+        const float* ang = io.angles[k] + (long)bb * io.ang_s0[k];
+        const int as1 = io.ang_s1[k];
+#pragma unroll
+        for (int r = 0; r < RM; ++r) A[r] = r < nr ? ang[(long)r * as1] : 0.f;
+        const VmasVec rv = io.rot[k];
+        rot = ld_vec1(rv, bb);
+    }
+    nav_load<NA>(io, bb, P, G);
+    const V2 pk = nav_sel<NA>(P, k);
+    // target t is agent t (t < k) or t + 1: a uniform select between two static registers
+    V2 T[TM];
+    float C[TM];
+#pragma unroll
+    for (int t = 0; t < TM; ++t) {
+        const V2 pt = t + 1 < NA ? (t < k ? P[t] : P[t + 1]) : P[t];
+        const float rad = io.agents[t < k ? t : t + 1].radius;
+        T[t] = t < nt ? pt - pk : mk(0.f, 0.f);
+        C[t] = rad * rad;  // (r^2)
+    }
+    nav_head<NA>(io, bb, k, P, G, S + row);
+    if (io.what & VMAS_SCN_REWARD) nav_reward<NA>(io, b, valid, k, lane, od, P, G);
+    else if ((io.what & VMAS_SCN_DONE) && k == 0 && valid) moved(io.done, od.done)[b] = nav_done<NA>(io, P, G) ? 1 : 0;
+    // (loops fully unrolled with guarded bodies, never `break`: see k_flocking_fast)
+    if constexpr (NR > 0 && NT > 0) {
+#pragma unroll
+        for (int r = 0; r < NR; ++r) {
+            const float a = A[r] + rot;
+            float ds, dc;
+            nav_sincos(a, ds, dc);
+            float best = io.max_range;
+#pragma unroll
+            for (int t = 0; t < NT; ++t) best = min_drop_nan(best, nav_ray_nan(T[t].x, T[t].y, C[t], dc, ds));
+            S[row + H + r] = best;
+        }
+    } else {
+        // rays in a rolled loop, targets unrolled inside; the angles wait in the rays' own LDS slots
+#pragma unroll
+        for (int r = 0; r < RM; ++r)
+            if (r < nr) S[row + H + r] = A[r] + rot;
+#pragma unroll 1
+        for (int r = 0; r < nr; ++r) {
+            const float a = S[row + H + r];
+            float ds, dc;
+            nav_sincos(a, ds, dc);
+            float best = io.max_range;
+#pragma unroll
+            for (int t = 0; t < TM; ++t) {
+                if (t >= nt) continue;
+                best = min_drop_nan(best, nav_ray_nan(T[t].x, T[t].y, C[t], dc, ds));
+            }
+            S[row + H + r] = best;
+        }
+    }
+    // the wave's rows out as contiguous blocks: obs [64 x W] (its LIDAR columns max_range - the
+    // measurement), the measurements [64 x nr]
+    const int nv = io.batch - g0 < 64 ? io.batch - g0 : 64;
+    float* obs = moved(io.obs[k], od.obs) + (long)g0 * W;
+    for (int i = lane; i < nv * W; i += 64) {
+        const int c = i - (i / W) * W;
+        const float v = S[i];
+        obs[i] = c >= H ? io.max_range - v : v;
+    }
+    if (nr > 0) {
+        float* lid = io.lidar[k] + (long)g0 * nr;
+        for (int i = lane; i < nv * nr; i += 64) {
+            const int e = i / nr;
+            lid[i] = S[e * W + H + (i - e * nr)];
+        }
+    }
+}
+
 // flocking's scripted target: u = stack([cos(t / period), sin(t / period)], dim=1) (the division
 // by a Python scalar as torch's divide kernel computes it: t * (1 / period) in fp32).
 __global__ void __launch_bounds__(256) k_flocking_target(const float* t, int batch, float inv, float* u) {
@@ -888,6 +1300,44 @@ int32_t vmas_flocking_outputs(int32_t device, const VmasFlockingIO* io, void* st
     } else
         hipLaunchKernelGGL(k_flocking, dim3((io->batch + 63) / 64, io->n_policy * parts), dim3(64), 0, (hipStream_t)stream,
                            *io);
+    VMAS_AUX_HIP(hipGetLastError());
+    return VMAS_OK;
+}
+
+int32_t vmas_navigation_outputs(int32_t device, const VmasNavigationIO* io, void* stream) {
+    if (!io || device < 0 || io->batch <= 0 || io->n_agents < 1 || io->n_agents > VMAS_NAV_MAX_AGENTS || io->n_rays < 0 ||
+        ((io->what & VMAS_SCN_REWARD) && !io->ws))
+        return vmas_aux::fail(VMAS_E_INVALID, "vmas_navigation_outputs: bad arguments");
+    for (int i = 0; i < io->n_agents; ++i) {
+        if (io->agents[i].shape != VMAS_SPHERE)
+            return vmas_aux::fail(VMAS_E_INVALID, "vmas_navigation_outputs: agent %d is not a sphere", i);
+        if (io->pair_static[i] >> i)
+            return vmas_aux::fail(VMAS_E_INVALID, "vmas_navigation_outputs: pair flags of agent %d name no earlier agent", i);
+    }
+    VMAS_AUX_HIP(hipSetDevice(device));
+    static_assert(sizeof(VmasNavigationIO) <= 4096, "kernel argument block");
+    const hipStream_t st = (hipStream_t)stream;
+    const int n = io->n_agents, nr = io->lidar_on ? io->n_rays : 0;
+    const int W = 4 + 2 * (io->observe_all_goals ? n : 1) + nr;
+    if (io->fast_lidar && nr <= kNavFastRays) {
+        const dim3 grid((io->batch + 63) / 64, (n + 3) / 4);
+        const size_t lds = (size_t)4 * 64 * W * sizeof(float);
+        // 12 rays with 1..7 targets (2..8 agents): the unrolled instantiation (other counts: runtime form)
+        switch (nr == 12 ? n - 1 : 0) {
+#define VMAS_NAV_CASE(t) \
+    case t: hipLaunchKernelGGL((k_navigation_fast<12, t>), grid, dim3(256), lds, st, *io); break;
+            VMAS_NAV_CASE(1) VMAS_NAV_CASE(2) VMAS_NAV_CASE(3) VMAS_NAV_CASE(4)
+            VMAS_NAV_CASE(5) VMAS_NAV_CASE(6) VMAS_NAV_CASE(7)
+#undef VMAS_NAV_CASE
+            default: hipLaunchKernelGGL((k_navigation_fast<0, 0>), grid, dim3(256), lds, st, *io); break;
+        }
+    } else {
+        const int parts = (io->what & VMAS_SCN_OBS) ? 1 + nr : 1;
+        hipLaunchKernelGGL(k_navigation, dim3((io->batch + 63) / 64, n * parts), dim3(64), 0, st, *io);
+    }
+    bool pairs = false;  // (no pair passes the static part of World.collides: nothing to settle)
+    for (int i = 0; i < n; ++i) pairs = pairs || io->pair_static[i] != 0u;
+    if ((io->what & VMAS_SCN_REWARD) && pairs) hipLaunchKernelGGL(k_navigation_pairs, dim3(1), dim3(1024), 0, st, *io);
     VMAS_AUX_HIP(hipGetLastError());
     return VMAS_OK;
 }

@@ -127,9 +127,9 @@ _STEP_METHODS = ("reward", "observation", "done", "info", "pre_step", "post_step
 
 # The scenarios whose step code the replay trusts beyond the watched eager step (write-only
 # attributes, direct outputs): the four benchmark scenarios, each held to its eager step by
-# tests/test_graph.py (not every file of the scenarios directory -- the debug scenarios
-# are replayed like a user's scenario).
-_TRUSTED_FILES = ("balance.py", "transport.py", "discovery.py", "flocking.py")
+# tests/test_graph.py, and navigation, held to it by tests/test_navigation_gpu.py (not
+# every file of the scenarios directory -- the debug scenarios are replayed like a user's scenario).
+_TRUSTED_FILES = ("balance.py", "transport.py", "discovery.py", "flocking.py", "navigation.py")
 
 
 def _trusted_scenario(scenario) -> bool:
