@@ -48,8 +48,9 @@ extern "C" {
  * v8: VmasRenderPrim / VmasRenderEntity / VmasRenderLidar / VmasRenderScene, vmas_render_frames,
  *     vmas_render_scene
  * v9: VmasMaskedSpan / vmas_masked_rows, VmasBalanceResetIO / vmas_balance_reset
- * v10: VmasNavigationIO / vmas_navigation_outputs */
-#define VMAS_ABI_VERSION 10
+ * v10: VmasNavigationIO / vmas_navigation_outputs
+ * v11: VmasTransportIO rew_attr */
+#define VMAS_ABI_VERSION 11
 
 /* error codes */
 #define VMAS_OK 0
@@ -739,6 +740,9 @@ typedef struct VmasTransportIO {
     const int64_t* out_delta;            /* optional (v5; graph mode's direct outputs): three device words,
                                              the byte offsets added to the obs / rewards / done pointers
                                              (simulator/environment/_graph.py DirectOutputs); NULL: none */
+    float* rew_attr;                     /* optional (v11): [B], the reward once more, at this address as it is
+                                             (no out_delta): Scenario.rew of a graph-mode step, whose replays
+                                             move `rew` into fresh output tensors; NULL: none */
 } VmasTransportIO;
 int32_t vmas_transport_outputs(int32_t device, const VmasTransportIO* io, void* stream);
 

@@ -162,6 +162,21 @@ class ScenarioParity:
         self.rec["steps"] += 1
         return out, exp
 
+    def evaluate(self):
+        """The program alone, on the state as it stands (no physics step, no actions): the oracle's
+        program and the product's (Environment.get_from_scenario) on the same snapshot -- for
+        hand-placed states that sit on the flags' thresholds by construction
+        (tests/_scenario_places.py) and that a step would move off them.  Both sides advance what
+        the program carries (shaping, discovery's respawn and all-time flags, flocking's t)."""
+        env, w, prog = self.env, self.env.world, self.prog
+        pre = O.snapshot(w)
+        out = env.get_from_scenario(get_observations=True, get_rewards=True, get_infos=True, get_dones=True)
+        post = O.snapshot(w)  # (discovery's reward respawns the covered targets)
+        exp = prog.step(pre, post)
+        self._check_outputs(out, exp, pre, post)
+        self.rec["steps"] += 1
+        return out, exp
+
     # ---- the action path ------------------------------------------------------------------------
     def _check_actions(self, acts, scripted_u):
         env, w = self.env, self.env.world

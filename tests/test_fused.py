@@ -128,10 +128,11 @@ def test_fused_balance_cache_follows_state_changes_gpu(gpu_device):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("n", [3, 4, 7, 8, 12])
+@pytest.mark.parametrize("n", [3, 4, 7, 8, 12, 1, 2, 5, 15, 16])
 def test_reduce_order_probe_finds_torch_mean_order_gpu(gpu_device, n):
     """The fused kernels' mean over n contiguous values reproduces torch's .mean(-1) on the device
-    bit for bit in one of the ordered_sum modes (else the scenario would keep its torch program)."""
+    bit for bit in one of the ordered_sum modes (else the scenario would keep its torch program):
+    flocking's mean lengths for 1 to 15 policy agents, both ends and off the powers of two."""
     assert _fused.reduce_order(torch.device(gpu_device), n) is not None
 
 

@@ -281,3 +281,134 @@ def test_lidar_scan_certification_cpu():
     off = exp.clone()
     off[:8, 0] = torch.where(exp[:8, 0] < 0.2, exp[:8, 0] + 1e-3, exp[:8, 0] - 1e-3)
     assert not _scan_certify(env.world, snap, idx, ai, rays, prog.lidar, off, bad).any()
+
+
+# ---- shapes, options and branches that random steps at the default kwargs never reach ------------
+# The GPU tests of the fused programs (tests/test_fused_edges.py) take the scenarios' torch programs
+# as their bit-exact reference, so those programs are held to the oracle here at the same shapes
+# (caps, cap + 1, one agent, several packages, both reward modes, both LIDARs, ray counts off the
+# unrolled forms) and on hand-placed states that force each branch (tests/_scenario_places.py).
+SHAPES = [
+    ("balance", dict(n_agents=2)), ("balance", dict(n_agents=5)), ("balance", dict(n_agents=32)),
+    ("balance", dict(n_agents=33)),
+    ("transport", dict(n_agents=1, n_packages=1)), ("transport", dict(n_agents=3, n_packages=2)),
+    ("transport", dict(n_agents=16, n_packages=8)), ("transport", dict(n_agents=2, n_packages=9)),
+    ("discovery", dict(n_agents=1, n_targets=1, agents_per_target=1)),
+    ("discovery", dict(n_agents=3, n_targets=4, targets_respawn=False, shared_reward=True, time_penalty=-0.01,
+                       agents_per_target=1)),
+    ("discovery", dict(n_agents=3, n_targets=2, time_penalty=-1)),
+    ("discovery", dict(n_agents=16, n_targets=16, use_agent_lidar=True)),
+    ("discovery", dict(n_agents=7, n_targets=3, use_agent_lidar=True, n_lidar_rays_entities=17,
+                       n_lidar_rays_agents=5)),
+    ("discovery", dict(n_agents=10, n_targets=7)),  # 17 entities
+    ("flocking", dict(n_agents=1, n_obstacles=0)), ("flocking", dict(n_agents=2, n_obstacles=0)),
+    ("flocking", dict(n_agents=3, n_obstacles=1)), ("flocking", dict(n_agents=4, n_obstacles=8)),
+    ("flocking", dict(n_agents=7, n_obstacles=9)), ("flocking", dict(n_agents=15, n_obstacles=16, n_lidar_rays=5)),
+    ("flocking", dict(n_agents=4, n_obstacles=17)), ("flocking", dict(n_agents=4, n_obstacles=5, n_lidar_rays=17)),
+    ("flocking", dict(n_agents=4, n_obstacles=5, collision_reward=0)),
+]
+
+
+def _case_id(case):
+    return case[0] + "-" + "-".join(f"{k}{v}" for k, v in case[1].items())
+
+
+@pytest.mark.parametrize("name,kw", SHAPES, ids=[_case_id(c) for c in SHAPES])
+def test_scenario_shapes_and_options_match_oracle_cpu(name, kw):
+    env = _make(name, kw, None, "cpu", 65, seed=1)
+    _run(env, name, kw, 3, f"{_case_id((name, kw))} 65 envs cpu")
+
+
+PLACED = [
+    ("balance", dict(n_agents=3)),
+    ("transport", dict(n_agents=3, n_packages=1)), ("transport", dict(n_agents=2, n_packages=3)),
+    ("discovery", dict(n_agents=4, n_targets=3)),
+    ("discovery", dict(n_agents=4, n_targets=2, targets_respawn=False)),
+    ("discovery", dict(n_agents=3, n_targets=4, shared_reward=True, time_penalty=-0.01, agents_per_target=1)),
+    ("discovery", dict(n_agents=1, n_targets=1, agents_per_target=1)),
+    ("flocking", dict(n_agents=3)), ("flocking", dict(n_agents=1, n_obstacles=2)),
+    ("flocking", dict(n_agents=2, n_obstacles=0)),
+]
+
+
+@pytest.mark.parametrize("name,kw", PLACED, ids=[_case_id(c) for c in PLACED])
+def test_programs_on_hand_placed_states_match_oracle_cpu(name, kw):
+    """The "true" side of every branch: the program alone on the placed state (no step between
+    placing and evaluating: a step moves the state off what was placed -- the world's bounds clamp
+    balance's lowered line back above the floor, covered targets respawn), then two random steps
+    from there, through discovery's respawn of the covered targets.  The placement's masks hold on
+    the product's outputs, each flag true in some env and false in another."""
+    from tests import _scenario_places as P
+
+    env = _make(name, kw, None, "cpu", 65, seed=5)
+    sp = ScenarioParity(env, name, kw)
+    masks = P.place(name, env)
+    out, exp = sp.evaluate()
+    flags = P.observed(name, env, out)
+    P.check(masks, flags, f"{name} program only")
+    if name == "transport" and kw["n_packages"] > 1:  # one package on, another off, in the same env
+        assert (flags["on_goal_0"] & ~flags["on_goal_1"]).any()
+    if name == "discovery" and not kw.get("targets_respawn", True):
+        assert out[2][16:24].all() and not out[2].all()  # (done: both targets covered at some time)
+    assert sp.ok and sp.rec["certified_envs"] == 0, sp.rec  # (no placed env within MARGIN_TOL of a threshold)
+    for _ in range(2):
+        sp.step()
+    rec = sp.record(f"{_case_id((name, kw))} 65 envs cpu, hand-placed")
+    assert sp.ok, f"{sp.failures[:6]!r} {rec!r}"
+    if name == "discovery" and kw.get("targets_respawn", True):
+        assert rec["respawn"]["respawned"] >= 8 and rec["respawn"]["bad_envs"] == 0, rec
+
+
+def test_program_entry_points_refuse_bad_arguments():
+    """Counts over a cap, a sum mode that is no power of two and a non-sphere flocking agent are
+    refused with VMAS_E_INVALID before any device call (so no GPU is needed and nothing is
+    launched).  Each struct is otherwise acceptable: with the counts in range the entry point gets
+    past its argument gate and names the deliberately wrong shape / index instead."""
+    import ctypes
+
+    from vectorizedmultiagentsimulator_amd import _native as N
+
+    lib = N.load_library()
+    VMAS_E_INVALID = -1
+
+    def refused(fn, io, message):
+        assert getattr(lib, fn)(0, ctypes.byref(io), None) == VMAS_E_INVALID, fn
+        assert message in lib.vmas_aux_last_error(), (fn, lib.vmas_aux_last_error())
+
+    b = N.VmasBalanceIO()
+    b.batch, b.n_agents, b.what = 4, 2, N.VMAS_SCN_OBS
+    refused("vmas_balance_outputs", b, b"unexpected entity shapes")  # (the gate passed)
+    b.n_agents = N.VMAS_SCN_MAX_AGENTS + 1
+    refused("vmas_balance_outputs", b, b"bad arguments")
+
+    t = N.VmasTransportIO()
+    t.batch, t.n_agents, t.n_packages, t.what = 4, 2, 1, N.VMAS_SCN_OBS
+    t.package[0].shape = t.goal[0].shape = N.VMAS_SPHERE
+    refused("vmas_transport_outputs", t, b"package 0 is not (box, sphere goal)")
+    t.n_agents = N.VMAS_TRANSPORT_MAX_AGENTS + 1
+    refused("vmas_transport_outputs", t, b"bad arguments")
+    t.n_agents, t.n_packages = 2, N.VMAS_TRANSPORT_MAX_PACKAGES + 1
+    refused("vmas_transport_outputs", t, b"bad arguments")
+
+    d = N.VmasDiscoveryIO()
+    d.batch, d.n_agents, d.n_targets, d.n_entities, d.n_lidars, d.what = 4, 1, 1, 2, 1, N.VMAS_SCN_OBS
+    d.agent_entity[0] = -1
+    refused("vmas_discovery_outputs", d, b"bad agent index 0")
+    d.n_targets = N.VMAS_DISC_MAX_TARGETS + 1
+    refused("vmas_discovery_outputs", d, b"bad arguments")
+
+    f = N.VmasFlockingIO()
+    f.batch, f.n_all, f.n_policy, f.target, f.n_rays, f.n_ray_targets, f.sum_mode = 4, 3, 2, 0, 12, 1, 2
+    f.what = N.VMAS_SCN_OBS
+    for i in range(3):
+        f.agents[i].shape = N.VMAS_SPHERE
+    f.agents[1].shape = N.VMAS_BOX
+    refused("vmas_flocking_outputs", f, b"agent 1 is not a sphere")
+    f.agents[1].shape = N.VMAS_SPHERE
+    f.n_ray_targets = N.VMAS_SCN_MAX_RAY_TARGETS + 1
+    refused("vmas_flocking_outputs", f, b"bad arguments")
+    f.n_ray_targets, f.sum_mode = 1, 3
+    refused("vmas_flocking_outputs", f, b"bad arguments")
+    f.sum_mode = 2
+    f.ray_targets[0].shape = N.VMAS_BOX  # (back past the gate: the counts above were what it refused)
+    refused("vmas_flocking_outputs", f, b"LIDAR target 0 is not a sphere")

@@ -19,7 +19,7 @@ LIB_PATH = Path(os.environ.get("VMAS_LIB_PATH") or Path(__file__).resolve().pare
 
 # ------------------------------------------------------------------------------------------------
 # constants mirrored from include/vmas_mi355x.h
-VMAS_ABI_VERSION = 10
+VMAS_ABI_VERSION = 11
 VMAS_SPHERE, VMAS_BOX, VMAS_LINE = 0, 1, 2
 (
     VMAS_PAIR_JOINT,
@@ -529,6 +529,7 @@ class VmasTransportIO(ctypes.Structure):
         ("dist_to_goal", _vp * _TP), ("on_goal", _vp * _TP), ("color", _vp * _TP), ("on_goal_in", _vp * _TP),
         ("rew", _vp), ("obs", _vp * _TA), ("done", _vp),
         ("out_delta", _vp),  # (graph mode's direct outputs: [obs, rewards, done] byte offsets)
+        ("rew_attr", _vp),  # (Scenario.rew of a graph-mode step: the reward at a fixed address too)
     ]
 
 

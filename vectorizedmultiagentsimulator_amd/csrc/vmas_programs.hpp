@@ -366,6 +366,7 @@ __device__ __forceinline__ void tr_reward_done(IO& io, int b, const OutDelta& od
             all_on = all_on && on;
         }
         moved(io.rew, od.rew)[b] = rew;
+        if (io.rew_attr) io.rew_attr[b] = rew;  // (Scenario.rew when a replay moves the output: transport.py)
     } else if (io.what & VMAS_SCN_DONE) {
         for (int i = 0; i < np; ++i) all_on = all_on && io.on_goal_in[i][b] != 0;
     }

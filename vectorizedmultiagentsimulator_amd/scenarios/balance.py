@@ -429,6 +429,8 @@ class Scenario(BaseScenario):
         if c is not None and c["done"] is not None and c["done_key"] == _fused.state_key(self._done_inputs()):
             d, c["done"] = c["done"], None
             return d
+        if len(self.world.agents) > N.VMAS_SCN_MAX_AGENTS:  # (over the argument block's cap: the torch program)
+            return self.on_the_ground + self.world.is_overlapping(self.package, self.package.goal)
         return self._run_fused(N.VMAS_SCN_DONE)["done"]
 
     def info(self, agent: Agent):

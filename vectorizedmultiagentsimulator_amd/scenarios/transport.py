@@ -177,6 +177,10 @@ class Scenario(BaseScenario):
         if what & N.VMAS_SCN_REWARD:
             out["rew"] = direct[1][0] if direct[1] else torch.empty(B, device=dev, dtype=torch.float32)
             io.rew = out["rew"].data_ptr()
+            # (a capture: the replays move the reward output into fresh tensors, away from the captured
+            # one, so self.rew gets a tensor of its own that every replay writes at its own address)
+            out["rew_attr"] = torch.empty(B, device=dev, dtype=torch.float32) if direct[1] else out["rew"]
+            io.rew_attr = out["rew_attr"].data_ptr() if direct[1] else None
         if what & N.VMAS_SCN_OBS:
             W = 4 + 7 * len(self.packages)
             out["obs"] = direct[0] or [torch.empty(B, W, device=dev, dtype=torch.float32) for _ in w.agents]
@@ -195,7 +199,8 @@ class Scenario(BaseScenario):
             _fused.check(_fused.lib().vmas_transport_outputs(dev.index, ctypes.byref(io), _fused.stream(w)),
                          "vmas_transport_outputs")
         if what & N.VMAS_SCN_REWARD:
-            self.rew = out["rew"]
+            self.rew = out["rew_attr"]
+            self._rew_out = (self.rew, out["rew"])  # (the tensor reward() returns while self.rew is this launch's)
             for i, p in enumerate(self.packages):
                 p.dist_to_goal = out["dist"][i]
                 p.on_goal = out["on_goal"][i]
@@ -208,7 +213,8 @@ class Scenario(BaseScenario):
             out = self._run_fused(N.VMAS_SCN_REWARD | N.VMAS_SCN_OBS | N.VMAS_SCN_DONE)
             self._fc = {"key": _fused.state_key(self._obs_inputs()), "obs": dict(enumerate(out["obs"])),
                         "done": out["done"]}
-        return self.rew
+        attr, ret = getattr(self, "_rew_out", None) or (None, None)
+        return ret if attr is self.rew else self.rew
 
     def _fused_observation(self, agent: Agent):
         i = self.world.agents.index(agent)
