@@ -49,8 +49,9 @@ extern "C" {
  *     vmas_render_scene
  * v9: VmasMaskedSpan / vmas_masked_rows, VmasBalanceResetIO / vmas_balance_reset
  * v10: VmasNavigationIO / vmas_navigation_outputs
- * v11: VmasTransportIO rew_attr */
-#define VMAS_ABI_VERSION 11
+ * v11: VmasTransportIO rew_attr
+ * v12: VmasActionProgramRef / vmas_action_programs, VmasVelocityPidRef / vmas_velocity_pid */
+#define VMAS_ABI_VERSION 12
 
 /* error codes */
 #define VMAS_OK 0
@@ -383,6 +384,74 @@ int32_t vmas_apply_discrete_actions(int32_t device, int32_t batch, const VmasDis
 int32_t vmas_apply_discrete_actions_launch(int32_t device, int32_t batch, const VmasDiscreteActionRef* refs,
                                            int32_t n_refs, float* out, int32_t mode, uint32_t* seq,
                                            void* stream);
+
+/* Action programs (csrc/vmas_action_programs.hip): the kinematic dynamics models that turn
+ * agent.action.u into the force / torque World.step reads (reference dynamics/diff_drive.py,
+ * kinematic_bicycle.py, drone.py), one launch for n_refs agents (at most 8 refs per launch; more
+ * are issued in chunks), one thread per (env, ref).  Per env row: the model's one-step increment
+ * (Euler: dt f(s); RK4: (dt / 6)(k1 + 2 k2 + 2 k3 + k4)) of the pose (pos, rot) -- for the drone of
+ * its 12 states, after u[:, 0] += mass_g and pos / rot were written into columns X, Y, PSI of
+ * drone_in, with drone_out = drone_in + increment -- and force = mass * (delta - vel dt) / dt^2,
+ * torque = moment_of_inertia * (dtheta - ang_vel dt) / dt^2.  Every operation is the reference's
+ * fp32 operation in its order.  The scalar fields hold the fp32 values torch makes of the
+ * reference's Python numbers (evaluated in double, rounded once); div_mode selects how a tensor is
+ * divided by such a number: 0 divides, 1 multiplies by the fp32 reciprocal inv_* (what a torch
+ * build does on its device, and whether its reciprocal is 1.0f / f32(d) or f32(1.0 / d), is probed
+ * by the caller).  device < 0 runs the host backend.
+ * VMAS_E_INVALID (nothing launched or written) for n_refs <= 0, a null pointer, a negative stride,
+ * an unknown kind / integration / div_mode. */
+#define VMAS_DYNAMICS_DIFF_DRIVE 0
+#define VMAS_DYNAMICS_BICYCLE 1
+#define VMAS_DYNAMICS_DRONE 2
+#define VMAS_INTEGRATION_EULER 0
+#define VMAS_INTEGRATION_RK4 1
+typedef struct VmasActionProgramRef {
+    float* u;             /* [B, >= 2] (drone: >= 4) action; the drone's column 0 is written */
+    const float* pos;     /* [B, 2] */
+    const float* vel;     /* [B, 2] */
+    const float* rot;     /* [B, 1] */
+    const float* ang_vel; /* [B, 1] */
+    float* force;         /* [B, 2], written through its strides */
+    float* torque;        /* [B, 1] contiguous, written */
+    float* drone_in;      /* drone: [B, 12] contiguous current state (columns 2, 9, 10 written) */
+    float* drone_out;     /* drone: [B, 12] contiguous new state */
+    int64_t u_s0, u_s1, pos_s0, pos_s1, vel_s0, vel_s1, rot_s0, ang_s0, force_s0, force_s1; /* element strides */
+    int32_t kind;         /* VMAS_DYNAMICS_* */
+    int32_t integration;  /* VMAS_INTEGRATION_* */
+    int32_t div_mode;
+    int32_t pad;
+    float mass, moment_of_inertia;
+    float dt, dt2, inv_dt2, dt_6;                     /* dt, dt ** 2, its reciprocal, dt / 6 */
+    float l_r, wheelbase, inv_wheelbase, max_steering_angle; /* bicycle (wheelbase = l_f + l_r) */
+    float inv_mass, g, mass_g;                        /* drone: the reciprocal of mass, g, mass * g */
+    float i_yz, i_zx, i_xy;                           /* drone: I_yy - I_zz, I_zz - I_xx, I_xx - I_yy */
+    float i_xx, i_yy, i_zz, inv_i_xx, inv_i_yy, inv_i_zz;
+} VmasActionProgramRef;
+
+int32_t vmas_action_programs(int32_t device, int32_t batch, const VmasActionProgramRef* refs, int32_t n_refs,
+                             void* stream);
+
+/* The PID velocity controller's process_force (reference controllers/velocity_controller.py), one
+ * launch, one thread per element of the [B, dim] error: e = u - vel; with the integrator accum +=
+ * dt e in place, then (accum_clamped != NULL) its clamp to +-cutoff written to accum_clamped, and
+ * I = inv_ti * accum; D = t_d (e - prev_err) / dt (div_mode as above); err_out = e and u_out =
+ * (gain (e + I + D)) * mass.  accum, accum_clamped, prev_err, err_out and u_out are contiguous
+ * [B, dim].  device < 0 runs the host backend; VMAS_E_INVALID for a null pointer, a negative
+ * stride or a bad dim / div_mode. */
+typedef struct VmasVelocityPidRef {
+    const float* u;         /* [B, dim] desired velocity (any strides) */
+    const float* vel;       /* [B, dim] (any strides) */
+    float* u_out;
+    float* err_out;         /* the new prev_err */
+    const float* prev_err;
+    float* accum;           /* in / out; may be NULL without the integrator */
+    float* accum_clamped;   /* NULL: no windup cutoff */
+    int64_t u_s0, u_s1, vel_s0, vel_s1;
+    int32_t dim, use_integrator, div_mode, pad;
+    float gain, inv_ti, t_d, dt, inv_dt, cutoff, mass, pad2;
+} VmasVelocityPidRef;
+
+int32_t vmas_velocity_pid(int32_t device, int32_t batch, const VmasVelocityPidRef* ref, void* stream);
 
 /* Random actions (Environment.get_random_actions, environment.py:524-606): the uniform_ draws
  * of every agent's action columns in one launch (csrc/vmas_actions.hip).  Column i gets

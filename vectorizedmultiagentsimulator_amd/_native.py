@@ -19,7 +19,7 @@ LIB_PATH = Path(os.environ.get("VMAS_LIB_PATH") or Path(__file__).resolve().pare
 
 # ------------------------------------------------------------------------------------------------
 # constants mirrored from include/vmas_mi355x.h
-VMAS_ABI_VERSION = 11
+VMAS_ABI_VERSION = 12
 VMAS_SPHERE, VMAS_BOX, VMAS_LINE = 0, 1, 2
 (
     VMAS_PAIR_JOINT,
@@ -130,6 +130,8 @@ EXPORTED_SYMBOLS = (
     "vmas_render_scene",
     "vmas_masked_rows",
     "vmas_balance_reset",
+    "vmas_action_programs",
+    "vmas_velocity_pid",
 )
 
 _i32 = ctypes.c_int32
@@ -647,6 +649,44 @@ DISCRETE_ACTION_REF_DTYPE = np.dtype(
 UNIFORM_COLUMN_DTYPE = np.dtype([("out", "<u8"), ("stride", "<i8"), ("from_", "<f4"), ("to", "<f4"), ("offset", "<u8"),
                                  ("u_out", "<u8"), ("u_stride", "<i8"), ("u_range", "<f4"), ("u_mult", "<f4"),
                                  ("u_clamp", "<i4"), ("pad", "<i4")])
+# action programs (csrc/vmas_action_programs.hip)
+DYNAMICS_DIFF_DRIVE, DYNAMICS_BICYCLE, DYNAMICS_DRONE = range(3)
+INTEGRATION_EULER, INTEGRATION_RK4 = 0, 1
+ACTION_PROGRAM_MAX_REFS = 8  # refs per launch; the library chunks above that
+ACTION_PROGRAM_REF_DTYPE = np.dtype(
+    [(k, "<u8") for k in ("u", "pos", "vel", "rot", "ang_vel", "force", "torque", "drone_in", "drone_out")]
+    + [(k, "<i8") for k in ("u_s0", "u_s1", "pos_s0", "pos_s1", "vel_s0", "vel_s1", "rot_s0", "ang_s0", "force_s0",
+                            "force_s1")]
+    + [(k, "<i4") for k in ("kind", "integration", "div_mode", "pad")]
+    + [(k, "<f4") for k in ("mass", "moment_of_inertia", "dt", "dt2", "inv_dt2", "dt_6", "l_r", "wheelbase",
+                            "inv_wheelbase", "max_steering_angle", "inv_mass", "g", "mass_g", "i_yz", "i_zx", "i_xy",
+                            "i_xx", "i_yy", "i_zz", "inv_i_xx", "inv_i_yy", "inv_i_zz")]
+)
+VELOCITY_PID_REF_DTYPE = np.dtype(
+    [(k, "<u8") for k in ("u", "vel", "u_out", "err_out", "prev_err", "accum", "accum_clamped")]
+    + [(k, "<i8") for k in ("u_s0", "u_s1", "vel_s0", "vel_s1")]
+    + [(k, "<i4") for k in ("dim", "use_integrator", "div_mode", "pad")]
+    + [(k, "<f4") for k in ("gain", "inv_ti", "t_d", "dt", "inv_dt", "cutoff", "mass", "pad2")]
+)
+assert ACTION_PROGRAM_REF_DTYPE.itemsize == 256
+assert VELOCITY_PID_REF_DTYPE.itemsize == 136
+# calls of the two entry points made through action_programs() / velocity_pid() (tests count launches)
+ACTION_PROGRAM_CALLS = {"vmas_action_programs": 0, "vmas_velocity_pid": 0}
+
+
+def action_programs(device_index: int, batch: int, refs: np.ndarray, stream) -> int:
+    """One vmas_action_programs call for the rows of an ACTION_PROGRAM_REF_DTYPE array; returns the
+    library's code (0, or VMAS_E_*: check_aux gives the message)."""
+    ACTION_PROGRAM_CALLS["vmas_action_programs"] += 1
+    return load_library().vmas_action_programs(device_index, batch, refs.ctypes.data, len(refs), stream)
+
+
+def velocity_pid(device_index: int, batch: int, ref: np.ndarray, stream) -> int:
+    """One vmas_velocity_pid call for a one-row VELOCITY_PID_REF_DTYPE array."""
+    ACTION_PROGRAM_CALLS["vmas_velocity_pid"] += 1
+    return load_library().vmas_velocity_pid(device_index, batch, ref.ctypes.data, stream)
+
+
 assert UNIFORM_COLUMN_DTYPE.itemsize == 64
 assert ACTION_REF_DTYPE.itemsize == 40
 assert ACTION_APPLY_REF_DTYPE.itemsize == 56
@@ -845,6 +885,10 @@ def load_library(path: os.PathLike | str | None = None) -> ctypes.CDLL:
     lib.vmas_jit_world_epilogue.argtypes = [_vp]
     lib.vmas_jit_program_outputs.restype = _i32
     lib.vmas_jit_program_outputs.argtypes = [_vp, _i32, _vp, _vp]
+    lib.vmas_action_programs.restype = _i32
+    lib.vmas_action_programs.argtypes = [_i32, _i32, _vp, _i32, _vp]
+    lib.vmas_velocity_pid.restype = _i32
+    lib.vmas_velocity_pid.argtypes = [_i32, _i32, _vp, _vp]
     ver = lib.vmas_abi_version()
     if ver != VMAS_ABI_VERSION:
         raise NativeLibraryError(f"ABI version mismatch: library {ver}, python {VMAS_ABI_VERSION}")

@@ -16,6 +16,7 @@ from typing import Optional
 
 import torch
 
+from .. import _action_programs as AP
 from ..utils import TorchUtils
 
 
@@ -67,6 +68,13 @@ class VelocityController:
         return rate
 
     def process_force(self):
+        """The native program where it is selected (simulator/_action_programs.py), else the torch one."""
+        self.accum_errs = self.accum_errs.to(self.world.device)
+        self.prev_err = self.prev_err.to(self.world.device)
+        if not AP.pid(self):
+            self.process_force_torch()
+
+    def process_force_torch(self):
         self.accum_errs = self.accum_errs.to(self.world.device)
         self.prev_err = self.prev_err.to(self.world.device)
         err = self.agent.action.u - self.agent.state.vel

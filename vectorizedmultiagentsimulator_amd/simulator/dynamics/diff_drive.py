@@ -6,6 +6,7 @@ integrated over one step (Euler or RK4) and turned into the force / torque that 
 physics step follow it."""
 import torch
 
+from .. import _action_programs as AP
 from . import _integrators as I
 from .common import Dynamics
 
@@ -33,6 +34,11 @@ class DiffDrive(Dynamics):
         return 2
 
     def process_action(self):
+        """The native program where it is selected (simulator/_action_programs.py), else the torch one."""
+        if not AP.dynamics(self):
+            self.process_action_torch()
+
+    def process_action_torch(self):
         u = self.agent.action.u
         delta = I.increment(self.f, I.pose(self.agent), self.dt, self.integration, u[:, 0], u[:, 1])
         I.apply_displacement(self.agent, delta[:, 0], delta[:, 1], delta[:, 2], self.dt)

@@ -11,6 +11,7 @@ import torch
 from torch import Tensor
 
 from .. import utils
+from .. import _action_programs as AP
 from . import _integrators as I
 from .common import Dynamics
 
@@ -70,6 +71,11 @@ class Drone(Dynamics):
         return 4
 
     def process_action(self):
+        """The native program where it is selected (simulator/_action_programs.py), else the torch one."""
+        if not AP.dynamics(self):
+            self.process_action_torch()
+
+    def process_action_torch(self):
         u = self.agent.action.u
         thrust = u[:, 0]
         torque = u[:, 1:4]

@@ -7,6 +7,7 @@ x' = v cos(theta + beta), y' = v sin(theta + beta), theta' = v / (l_f + l_r) cos
 integrated over one step and turned into force / torque."""
 import torch
 
+from .. import _action_programs as AP
 from . import _integrators as I
 from .common import Dynamics
 
@@ -45,6 +46,11 @@ class KinematicBicycle(Dynamics):
         return 2
 
     def process_action(self):
+        """The native program where it is selected (simulator/_action_programs.py), else the torch one."""
+        if not AP.dynamics(self):
+            self.process_action_torch()
+
+    def process_action_torch(self):
         u = self.agent.action.u
         steer = torch.clamp(u[:, 1], -self.max_steering_angle, self.max_steering_angle)
         delta = I.increment(self.f, I.pose(self.agent), self.dt, self.integration, steer, u[:, 0])

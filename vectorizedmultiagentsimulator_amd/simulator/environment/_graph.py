@@ -19,7 +19,8 @@ What a replay must honour, and how:
     (integration, core.py:2866-2907; scenario attributes such as balance's ``global_shaping``).
     A captured program reads the tensors that were bound when it was captured (X) and writes
     tensors of the graph pool (Y).  At capture the attributes of the simulator's objects (env,
-    scenario, world, entities, entity states, agent actions, joint constraints) are diffed:
+    scenario, world, entities, entity states, agent actions, dynamics models, controllers, joint
+    constraints) are diffed:
     every attribute re-bound from X to Y is a carried tensor, and before each replay its current
     value is copied Y -> X (one multi-tensor copy, grouped by storage: the engine's whole output
     buffer is one copy).
@@ -89,6 +90,11 @@ def _tracked_objects(env) -> List[Any]:
             objs.append(a)
         for sensor in getattr(e, "_sensors", None) or ():  # Lidar._last_measurement is re-bound per step
             objs.append(sensor)
+        # a Drone's drone_state, a VelocityController's prev_err / accum_errs: re-bound per step
+        for name in ("dynamics", "controller"):
+            o = e.__dict__.get(name)
+            if o is not None:
+                objs.append(o)
     for jc in w._joints.values():
         objs.append(jc)
     seen = set()
@@ -725,8 +731,7 @@ class StepGraph:
     def body(self):
         """Everything of Environment.step after the actions (environment.py:394-412)."""
         env = self.env
-        for agent in env.world.agents:
-            env.scenario.env_process_action(agent)
+        env._process_actions()
         env.scenario.pre_step()
         env.world.step()
         env.scenario.post_step()

@@ -5,8 +5,8 @@ generator states would leave, and in every other env the row it held before -- f
 tensor of the simulation state.  A scenario without a ``reset_world_where`` of its own gets that
 from its ordinary full reset:
 
-  1. walk the tracked objects (graph mode's ``_tracked_objects`` plus every entity's dynamics and
-     controller) and record each attribute that is a tensor with leading dimension ``batch_dim``,
+  1. walk the tracked objects (graph mode's ``_tracked_objects``: every entity's dynamics and
+     controller included) and record each attribute that is a tensor with leading dimension ``batch_dim``,
      with its version counter and a copy of its values (the full reset may write it in place);
   2. run the full reset (``env_reset_world_at(None)``, ``steps = zeros``);
   3. merge: a tensor the reset re-bound still has its old object as the snapshot, one it wrote in
@@ -41,13 +41,6 @@ def tracked_objects(scenario, env=None) -> List[Any]:
         shim = _Shim()
         shim.world, shim.scenario = scenario.world, scenario
         objs = _tracked_objects(shim)[1:]
-    seen = {id(o) for o in objs}
-    for e in scenario.world.entities:
-        for name in ("dynamics", "controller"):
-            o = e.__dict__.get(name)
-            if o is not None and hasattr(o, "__dict__") and id(o) not in seen:
-                seen.add(id(o))
-                objs.append(o)
     return objs
 
 

@@ -25,6 +25,7 @@ import torch
 from torch import Tensor
 
 from ... import _native as N
+from .. import _action_programs
 from .. import core as _core
 from ..core import Agent, TorchVectorizedObject
 from ..scenario import BaseScenario
@@ -509,14 +510,31 @@ class Environment(TorchVectorizedObject):
                 self._validate_continuous_actions(actions)
             for i, agent in enumerate(self.agents):
                 self._set_action(actions[i], agent, validated=self.continuous_actions)
-        for agent in self.world.agents:
-            self.scenario.env_process_action(agent)
+        self._process_actions()
         self.scenario.pre_step()
         self.world.step()
         self.scenario.post_step()
         self.steps += 1
         return self._get_from_scenario(get_observations=True, get_infos=True, get_rewards=True,
                                        get_dones=True)
+
+    def _process_actions(self):
+        """env_process_action of every agent (both step loops).  When nothing can observe their
+        order -- no process_action of the scenario's own, no scripted agent -- the native dynamics
+        programs of all agents are collected and issued as one vmas_action_programs launch after
+        the loop; otherwise each launches where it runs (simulator/_action_programs.py)."""
+        scenario = self.scenario
+        with _action_programs.batch(_action_programs.batchable(self)):
+            for agent in self.world.agents:
+                scenario.env_process_action(agent)
+
+    @property
+    def action_programs(self) -> Dict[str, str]:
+        """Per agent name how its dynamics' process_action runs: "native" (one launch of the gfx950
+        action-program kernel), "torch: <reason>" (the reference's tensor program) or "none" (a
+        Holonomic-family model: nothing to compute); an agent with a controller has a second entry
+        "<name>.controller" for its process_force."""
+        return _action_programs.env_status(self)
 
     def _done(self):
         terminated = self.scenario.done()
