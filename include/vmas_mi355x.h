@@ -50,8 +50,9 @@ extern "C" {
  * v9: VmasMaskedSpan / vmas_masked_rows, VmasBalanceResetIO / vmas_balance_reset
  * v10: VmasNavigationIO / vmas_navigation_outputs
  * v11: VmasTransportIO rew_attr
- * v12: VmasActionProgramRef / vmas_action_programs, VmasVelocityPidRef / vmas_velocity_pid */
-#define VMAS_ABI_VERSION 12
+ * v12: VmasActionProgramRef / vmas_action_programs, VmasVelocityPidRef / vmas_velocity_pid
+ * v13: VmasSamplingIO / vmas_sampling_outputs, VmasSamplingMaxPdfIO / vmas_sampling_max_pdf */
+#define VMAS_ABI_VERSION 13
 
 /* error codes */
 #define VMAS_OK 0
@@ -1207,6 +1208,93 @@ typedef struct VmasBalanceResetIO {
     float* steps;              /* [B] contiguous, or NULL */
 } VmasBalanceResetIO;
 int32_t vmas_balance_reset(int32_t device, const VmasBalanceResetIO* io, uint64_t* increment, void* stream);
+
+/* ---- sampling (v13; reference vmas/scenarios/sampling.py `sample`, `reward`, `observation`,
+ * `nomrlize_pdf`; restated in scenarios/sampling.py) ------------------------------------------------
+ * The density of a point p in env b is the sum over the Gaussians g (isotropic, covariance cov_g I)
+ * of exp(-0.5 * (2 log(2 pi) + |(p - loc_g[b]) / L_g|^2) - (log L_g + log L_g)), L_g = sqrt(cov_g):
+ * the fp32 operations of MultivariateNormal.log_prob(p).exp() for such a covariance, each rounded
+ * on its own, summed in the order of torch's .sum(-1) over a contiguous [B, n] tensor (sum_mode: the
+ * accumulator count, simulator/_fused.py reduce_order).  A point's cell is
+ * trunc(p / grid_spacing + n_cells / 2) per axis (div_mode 1: p * inv_grid_spacing, as a torch build
+ * divides a tensor by a Python number on its device); a cell outside the grid is never read or
+ * written (the reference raises there). */
+#define VMAS_SAMPLING_MAX_AGENTS 16
+#define VMAS_SAMPLING_MAX_GAUSSIANS 8
+#define VMAS_SAMPLING_MAX_RAYS 16
+typedef struct VmasSamplingGrid {
+    int32_t n_x, n_y;       /* cells: sampled is [B, n_x, n_y] */
+    int32_t div_mode, pad0;
+    float xdim, ydim;           /* out of bounds: strictly outside +-xdim / +-ydim */
+    float x_semidim, y_semidim; /* positions are clamped to these */
+    float grid_spacing, inv_grid_spacing;
+    float half_nx, half_ny;     /* f32(n_x / 2), f32(n_y / 2) */
+} VmasSamplingGrid;
+typedef struct VmasSamplingDensity {
+    int32_t n_gaussians, sum_mode;
+    float log_norm; /* f32(2 log(2 pi)) */
+    float pad0;
+    float scale[VMAS_SAMPLING_MAX_GAUSSIANS];        /* L_g (the fp32 square root of f32(cov_g)) */
+    float half_log_det[VMAS_SAMPLING_MAX_GAUSSIANS]; /* fp32 log L_g + log L_g */
+    VmasVec loc[VMAS_SAMPLING_MAX_GAUSSIANS];        /* [B, 2] */
+} VmasSamplingDensity;
+/* vmas_sampling_outputs: in one launch, for every agent at once,
+ *   REWARD (Scenario.reward of the first agent): per agent in order sample(pos, update_sampled_flag,
+ *     norm): out-of-bounds test, the in-place clamp of pos, the cell, the density (over max_pdf when
+ *     norm), zero where the cell was sampled before the step or an earlier agent of this step is in
+ *     it or the point is out of bounds; every agent's cell marked; sampling_rew = the sum over the
+ *     agents; rewards[i] = sampling_rew (shared_rew) or sample[i];
+ *   OBS (Scenario.observation): pos, vel, the LIDAR over the other agents (as vmas_navigation_outputs:
+ *     fast_lidar 0 bit-identical to vmas_cast_rays, 1 within the LIDAR parity tolerance) and the 8
+ *     probes pos + d, d = (+s,0) (-s,0) (0,+s) (0,-s) (-s,-s) (+s,-s) (-s,+s) (+s,+s), each
+ *     sample(probe, norm = True) without flag updates.
+ * With REWARD | OBS the observation sees the clamped positions and the flags of this step (a probe is
+ * zero where its cell was sampled before or any agent is in it now).  Grid: a wave per (64 envs,
+ * agent); the first agent's wave also computes the reward block of its envs.  device -1: the host
+ * loop (exact LIDAR). */
+typedef struct VmasSamplingIO {
+    int32_t batch, n_agents, what, n_rays;
+    int32_t shared_rew, norm, lidar_on, fast_lidar;
+    int32_t agent_sum_mode, pad0; /* accumulators of the sum over the agents' samples */
+    float max_range, pad1;
+    VmasSamplingGrid grid;
+    VmasSamplingDensity density;
+    VmasMutVec pos[VMAS_SAMPLING_MAX_AGENTS]; /* [B,2] agent.state.pos: clamped in place (REWARD) */
+    float radius[VMAS_SAMPLING_MAX_AGENTS];   /* sphere radii (the LIDAR's targets) */
+    VmasVec vel[VMAS_SAMPLING_MAX_AGENTS];    /* [B,2] (OBS) */
+    VmasVec rot[VMAS_SAMPLING_MAX_AGENTS];    /* [B,1] (OBS, lidar_on) */
+    const float* angles[VMAS_SAMPLING_MAX_AGENTS]; /* [B, n_rays] (Lidar._angles) */
+    int32_t ang_s0[VMAS_SAMPLING_MAX_AGENTS], ang_s1[VMAS_SAMPLING_MAX_AGENTS];
+    const float* max_pdf;                     /* [B] contiguous */
+    uint8_t* sampled;                         /* [B, n_x, n_y] torch.bool contiguous, in place */
+    float* sample[VMAS_SAMPLING_MAX_AGENTS];  /* [B] fresh (REWARD): agent.sample */
+    float* sampling_rew;                      /* [B] fresh (REWARD) */
+    float* rewards[VMAS_SAMPLING_MAX_AGENTS]; /* [B] fresh (REWARD) */
+    float* obs[VMAS_SAMPLING_MAX_AGENTS];     /* [B, 4 + n_rays + 8] fresh (OBS) */
+    float* lidar[VMAS_SAMPLING_MAX_AGENTS];   /* [B, n_rays] fresh (OBS, lidar_on) */
+    int32_t* undo;                            /* optional (REWARD): [B, n_agents] contiguous; entry (b, j) = the
+                                                 cell (ix * n_y + iy) agent j marked where the flag was clear
+                                                 before the step, else -1: what undoing the step clears again
+                                                 (graph mode's rollback, in place of a per-step copy of sampled) */
+    const int64_t* out_delta;                 /* optional: as VmasNavigationIO.out_delta */
+} VmasSamplingIO;
+int32_t vmas_sampling_outputs(int32_t device, const VmasSamplingIO* io, void* stream);
+
+/* vmas_sampling_max_pdf (nomrlize_pdf): max_pdf[b] = max(0, the density of every grid point (xs[i],
+ * ys[j]) clamped to the semidims, zero for a point out of bounds), for the envs of `mask` ([B]
+ * torch.bool; NULL: every env); the other rows are neither read nor written.  xs / ys: the values of
+ * torch.arange(-dim, dim, grid_spacing).  One launch, a wave per env, lanes over the points, a
+ * wave-level NaN-propagating max (order-free).  device -1: the host loop. */
+typedef struct VmasSamplingMaxPdfIO {
+    int32_t batch, n_xs, n_ys, pad0;
+    VmasSamplingGrid grid;
+    VmasSamplingDensity density;
+    const float* xs;
+    const float* ys;
+    const uint8_t* mask;
+    float* max_pdf; /* [B] contiguous, in place */
+} VmasSamplingMaxPdfIO;
+int32_t vmas_sampling_max_pdf(int32_t device, const VmasSamplingMaxPdfIO* io, void* stream);
 
 #ifdef __cplusplus
 }

@@ -19,7 +19,7 @@ LIB_PATH = Path(os.environ.get("VMAS_LIB_PATH") or Path(__file__).resolve().pare
 
 # ------------------------------------------------------------------------------------------------
 # constants mirrored from include/vmas_mi355x.h
-VMAS_ABI_VERSION = 12
+VMAS_ABI_VERSION = 13
 VMAS_SPHERE, VMAS_BOX, VMAS_LINE = 0, 1, 2
 (
     VMAS_PAIR_JOINT,
@@ -84,6 +84,8 @@ EXPORTED_SYMBOLS = (
     "vmas_flocking_outputs",
     "vmas_flocking_target_action",
     "vmas_navigation_outputs",
+    "vmas_sampling_outputs",
+    "vmas_sampling_max_pdf",
     "vmas_assert_publish_range",
     "vmas_transport_outputs",
     "vmas_discovery_outputs",
@@ -516,6 +518,48 @@ class VmasNavigationIO(ctypes.Structure):
     ]
 
 
+VMAS_SAMPLING_MAX_AGENTS, VMAS_SAMPLING_MAX_GAUSSIANS, VMAS_SAMPLING_MAX_RAYS = 16, 8, 16
+_SA, _SG = VMAS_SAMPLING_MAX_AGENTS, VMAS_SAMPLING_MAX_GAUSSIANS
+
+
+class VmasSamplingGrid(ctypes.Structure):
+    _fields_ = [
+        ("n_x", _i32), ("n_y", _i32), ("div_mode", _i32), ("pad0", _i32),
+        ("xdim", _f32), ("ydim", _f32), ("x_semidim", _f32), ("y_semidim", _f32),
+        ("grid_spacing", _f32), ("inv_grid_spacing", _f32), ("half_nx", _f32), ("half_ny", _f32),
+    ]
+
+
+class VmasSamplingDensity(ctypes.Structure):
+    _fields_ = [
+        ("n_gaussians", _i32), ("sum_mode", _i32), ("log_norm", _f32), ("pad0", _f32),
+        ("scale", _f32 * _SG), ("half_log_det", _f32 * _SG), ("loc", VmasVec * _SG),
+    ]
+
+
+class VmasSamplingIO(ctypes.Structure):
+    _fields_ = [
+        ("batch", _i32), ("n_agents", _i32), ("what", _i32), ("n_rays", _i32),
+        ("shared_rew", _i32), ("norm", _i32), ("lidar_on", _i32), ("fast_lidar", _i32),
+        ("agent_sum_mode", _i32), ("pad0", _i32), ("max_range", _f32), ("pad1", _f32),
+        ("grid", VmasSamplingGrid), ("density", VmasSamplingDensity),
+        ("pos", VmasMutVec * _SA), ("radius", _f32 * _SA), ("vel", VmasVec * _SA), ("rot", VmasVec * _SA),
+        ("angles", _vp * _SA), ("ang_s0", _i32 * _SA), ("ang_s1", _i32 * _SA),
+        ("max_pdf", _vp), ("sampled", _vp),
+        ("sample", _vp * _SA), ("sampling_rew", _vp), ("rewards", _vp * _SA), ("obs", _vp * _SA), ("lidar", _vp * _SA),
+        ("undo", _vp),  # (the cells this step marked: graph mode's rollback)
+        ("out_delta", _vp),  # (graph mode's direct outputs: [obs, rewards, done] byte offsets)
+    ]
+
+
+class VmasSamplingMaxPdfIO(ctypes.Structure):
+    _fields_ = [
+        ("batch", _i32), ("n_xs", _i32), ("n_ys", _i32), ("pad0", _i32),
+        ("grid", VmasSamplingGrid), ("density", VmasSamplingDensity),
+        ("xs", _vp), ("ys", _vp), ("mask", _vp), ("max_pdf", _vp),
+    ]
+
+
 VMAS_TRANSPORT_MAX_PACKAGES = 8
 VMAS_TRANSPORT_MAX_AGENTS = 16
 _TP, _TA = VMAS_TRANSPORT_MAX_PACKAGES, VMAS_TRANSPORT_MAX_AGENTS
@@ -739,6 +783,10 @@ def load_library(path: os.PathLike | str | None = None) -> ctypes.CDLL:
     lib.vmas_flocking_outputs.argtypes = [_i32, _vp, _vp]
     lib.vmas_navigation_outputs.restype = _i32
     lib.vmas_navigation_outputs.argtypes = [_i32, _vp, _vp]
+    lib.vmas_sampling_outputs.restype = _i32
+    lib.vmas_sampling_outputs.argtypes = [_i32, _vp, _vp]
+    lib.vmas_sampling_max_pdf.restype = _i32
+    lib.vmas_sampling_max_pdf.argtypes = [_i32, _vp, _vp]
     lib.vmas_distance_vjp.restype = _i32
     lib.vmas_distance_vjp.argtypes = [_i32, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
     lib.vmas_cast_rays_vjp.restype = _i32

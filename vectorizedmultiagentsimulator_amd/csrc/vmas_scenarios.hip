@@ -1205,6 +1205,303 @@ __global__ void __launch_bounds__(256) k_discovery_obs_split(VmasDiscoveryIO io_
     for (int k = lane + s * 64; k < nv * W; k += 64 * L) obs[k] = S[sub][k];
 }
 
+// ---- sampling (sampling.py `sample` / `reward` / `observation` / `nomrlize_pdf`; restated in
+// scenarios/sampling.py) ---------------------------------------------------------------------------
+// The per-(env, agent) program and the grid-point density are host / device functions: the kernels
+// below and the host backend (device == -1) run the same statements.  IO is the argument block by
+// reference -- on the device read in place from the kernel argument segment (see k_flocking_fast).
+#define VMAS_SAMP_HD __host__ __device__ __forceinline__
+constexpr int kSampMA = VMAS_SAMPLING_MAX_AGENTS, kSampMG = VMAS_SAMPLING_MAX_GAUSSIANS;
+
+// torch.clamp_(x, -m, m): NaN stays NaN
+VMAS_SAMP_HD float samp_clamp(float x, float m) { return x != x ? x : fminf(fmaxf(x, -m), m); }
+// torch.maximum: NaN propagates
+VMAS_SAMP_HD float samp_max(float a, float b) { return (a != a) ? a : ((b != b || b > a) ? b : a); }
+
+template <class IO>
+VMAS_SAMP_HD bool samp_oob(IO& io, float x, float y) {
+    return (x < -io.grid.xdim) || (x > io.grid.xdim) || (y < -io.grid.ydim) || (y > io.grid.ydim);
+}
+// the cell of a (clamped) point as ix * n_y + iy, or -1 when it indexes past the grid (never read
+// or written: the reference raises there)
+template <class IO>
+VMAS_SAMP_HD int samp_cell(IO& io, float x, float y) {
+    const float gs = io.grid.grid_spacing, inv = io.grid.inv_grid_spacing;
+    const float fx = (io.grid.div_mode ? x * inv : x / gs) + io.grid.half_nx;
+    const float fy = (io.grid.div_mode ? y * inv : y / gs) + io.grid.half_ny;
+    // .to(torch.long) truncates towards zero; NaN fails every comparison
+    const bool ok = fx > -1.f && fx < (float)io.grid.n_x && fy > -1.f && fy < (float)io.grid.n_y;
+    return ok ? (int)fx * io.grid.n_y + (int)fy : -1;
+}
+// n floats summed as torch's .sum(-1) over a contiguous last dim: element j goes to accumulator
+// j % acc, the accumulators are combined by an adjacent-pair tree (see flock_part0; every value is
+// >= +0 or NaN, so 0 + e == e).  Static register indices only.
+template <int M>
+VMAS_SAMP_HD void samp_acc_add(float* y, int slot, float e) {
+#pragma unroll
+    for (int i = 0; i < M; ++i)
+        if (i == slot) y[i] = y[i] + e;
+}
+template <int M>
+VMAS_SAMP_HD float samp_acc_tree(float* y, int n, int acc) {
+    const int m = n < acc ? n : acc;
+#pragma unroll
+    for (int w = 1; w < M; w *= 2)
+#pragma unroll
+        for (int i = 0; i + w < M; i += 2 * w)
+            if (i + w < m) y[i] = y[i] + y[i + w];
+    return y[0];
+}
+// the unnormalised density of (x, y) in env b (include/vmas_mi355x.h, "sampling")
+template <class IO>
+VMAS_SAMP_HD float samp_density(IO& io, long b, float x, float y) {
+    float acc[kSampMG];
+#pragma unroll
+    for (int i = 0; i < kSampMG; ++i) acc[i] = 0.f;
+    const int ng = io.density.n_gaussians, am = io.density.sum_mode - 1;
+    const float c = io.density.log_norm;
+#pragma unroll 1
+    for (int g = 0; g < ng; ++g) {
+        const float* lp = io.density.loc[g].p;
+        const long s0 = io.density.loc[g].s0, s1 = io.density.loc[g].s1;
+        const float L = io.density.scale[g];
+        const float y0 = (x - lp[b * s0]) / L, y1 = (y - lp[b * s0 + s1]) / L;
+        const float M = y0 * y0 + y1 * y1;
+        const float lg = (-0.5f * (c + M)) - io.density.half_log_det[g];
+        samp_acc_add<kSampMG>(acc, g & am, expf(lg));
+    }
+    return samp_acc_tree<kSampMG>(acc, ng, io.density.sum_mode);
+}
+// sample(p, norm=False) of a grid point of nomrlize_pdf (the flags were cleared just before)
+template <class IO>
+VMAS_SAMP_HD float samp_grid_point(IO& io, long b, float x, float y) {
+    const bool oob = samp_oob(io, x, y);
+    const float v = samp_density(io, b, samp_clamp(x, io.grid.x_semidim), samp_clamp(y, io.grid.y_semidim));
+    return oob ? 0.f : v;
+}
+
+// Agent k in env b.  REWARD (k == 0 only; the reward block of every agent): flags are read before any
+// is written, an agent's sample is zero where its cell was sampled before or an earlier agent is in
+// it.  OBS: row `o` ([4 + n_rays + 8]) and, when `lid` is given, the LIDAR row.  Other (env, agent)
+// threads of the launch run beside this one: they read the positions this one clamps (clamping is
+// idempotent) and the flags it sets (a probe is zero where the cell was sampled before OR an agent is
+// in it now, whichever of the two the load returns).  Formally these cross-wave reads of `pos` and
+// `sampled` beside agent 0's stores are data races; they are benign by construction: every value is
+// a 4-byte (position) or 1-byte (flag) store, and either value a load can return gives the same
+// result.  Known costs, not measured apart: every (env, agent) thread reloads, clamps and cells all
+// NA agents (n^2 loads per env), and a lane writes its LDS row at a stride of W = 24 floats (8-way
+// bank conflicts on the row writes; the copy-out reads are conflict-free).
+template <int NA, class IO>
+VMAS_SAMP_HD void samp_agent(IO& io, long b, int k, float* o, float* lid, long long rew_delta) {
+    const int n = io.n_agents;
+    const bool rew = (io.what & VMAS_SCN_REWARD) != 0;
+    const float xs = io.grid.x_semidim, ys = io.grid.y_semidim;
+    float CX[NA], CY[NA];
+    int CELL[NA];
+    bool OOB[NA];
+#pragma unroll
+    for (int j = 0; j < NA; ++j) {
+        CX[j] = CY[j] = 0.f;
+        CELL[j] = -1;
+        OOB[j] = false;
+        if (j >= n) continue;
+        const float* pp = io.pos[j].p;
+        const long s0 = io.pos[j].s0, s1 = io.pos[j].s1;
+        float x = pp[b * s0], y = pp[b * s0 + s1];
+        if (rew) {
+            OOB[j] = samp_oob(io, x, y);
+            x = samp_clamp(x, xs);
+            y = samp_clamp(y, ys);
+            CELL[j] = samp_cell(io, x, y);
+        }
+        CX[j] = x;
+        CY[j] = y;
+    }
+    uint8_t* flags = io.sampled + b * ((long)io.grid.n_x * io.grid.n_y);
+    const float mp = io.max_pdf[b];
+    if (rew && k == 0) {
+        bool Z[NA], F[NA];
+#pragma unroll
+        for (int j = 0; j < NA; ++j) {
+            F[j] = CELL[j] >= 0 && flags[CELL[j]] != 0;
+            Z[j] = OOB[j] || F[j];
+#pragma unroll
+            for (int i = 0; i < j; ++i) Z[j] = Z[j] || (CELL[j] >= 0 && CELL[i] == CELL[j]);
+        }
+        float acc[NA];
+#pragma unroll
+        for (int j = 0; j < NA; ++j) acc[j] = 0.f;
+        float V[NA];
+        const int am = io.agent_sum_mode - 1;
+#pragma unroll
+        for (int j = 0; j < NA; ++j) {
+            V[j] = 0.f;
+            if (j >= n) continue;
+            float v = samp_density(io, b, CX[j], CY[j]);
+            if (io.norm) v = v / mp;
+            V[j] = Z[j] ? 0.f : v;
+            samp_acc_add<NA>(acc, j & am, V[j]);
+            float* pp = io.pos[j].p;
+            const long s0 = io.pos[j].s0, s1 = io.pos[j].s1;
+            pp[b * s0] = CX[j];
+            pp[b * s0 + s1] = CY[j];
+            io.sample[j][b] = V[j];
+            if (CELL[j] >= 0) flags[CELL[j]] = 1;
+            if (io.undo) io.undo[b * n + j] = (CELL[j] >= 0 && !F[j]) ? CELL[j] : -1;
+        }
+        const float s = samp_acc_tree<NA>(acc, n, io.agent_sum_mode);
+        io.sampling_rew[b] = s;
+#pragma unroll
+        for (int j = 0; j < NA; ++j)
+            if (j < n) reinterpret_cast<float*>(reinterpret_cast<char*>(io.rewards[j]) + rew_delta)[b] = io.shared_rew ? s : V[j];
+    }
+    if (!(io.what & VMAS_SCN_OBS)) return;
+    float px = 0.f, py = 0.f;
+#pragma unroll
+    for (int j = 0; j < NA; ++j)
+        if (j == k) {
+            px = CX[j];
+            py = CY[j];
+        }
+    const float* vp = io.vel[k].p;
+    const long vs0 = io.vel[k].s0, vs1 = io.vel[k].s1;
+    o[0] = px;
+    o[1] = py;
+    o[2] = vp[b * vs0];
+    o[3] = vp[b * vs0 + vs1];
+    const int nr = io.lidar_on ? io.n_rays : 0;
+    if (nr > 0) {
+        // Lidar.measure = World.cast_rays(angles + agent rot) over the other agents, in order
+        const float* ang = io.angles[k] + b * (long)io.ang_s0[k];
+        const long as1 = io.ang_s1[k];
+        const float rot = io.rot[k].p[b * (long)io.rot[k].s0];
+        const float mr = io.max_range;
+#pragma unroll 1
+        for (int r = 0; r < nr; ++r) {
+            const float a = ang[r * as1] + rot;
+            float best = mr;
+#ifdef __HIP_DEVICE_COMPILE__
+            if (io.fast_lidar) {
+                float ds, dc;
+                nav_sincos(a, ds, dc);
+#pragma unroll
+                for (int j = 0; j < NA; ++j) {
+                    if (j >= n || j == k) continue;
+                    const float rad = io.radius[j];
+                    best = min_drop_nan(best, nav_ray_nan(CX[j] - px, CY[j] - py, rad * rad, dc, ds));
+                }
+            } else
+#endif
+            {
+                const float dc = cosf(a), ds = sinf(a);
+#pragma unroll
+                for (int j = 0; j < NA; ++j)
+                    if (j < n && j != k) best = tmin(best, ray_sphere(mk(px, py), dc, ds, mk(CX[j], CY[j]), io.radius[j], mr));
+            }
+            o[4 + r] = best;
+            if (lid) lid[r] = best;
+        }
+    }
+    // the probes: sample(pos + d) with norm = True, no flag update
+    const float s = io.grid.grid_spacing;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const float dx = (i == 0 || i == 5 || i == 7) ? s : ((i == 1 || i == 4 || i == 6) ? -s : 0.f);
+        const float dy = (i == 2 || i == 6 || i == 7) ? s : ((i == 3 || i == 4 || i == 5) ? -s : 0.f);
+        float qx = px + dx, qy = py + dy;
+        bool z = samp_oob(io, qx, qy);
+        qx = samp_clamp(qx, xs);
+        qy = samp_clamp(qy, ys);
+        const int c = samp_cell(io, qx, qy);
+        if (c >= 0) {
+            z = z || flags[c] != 0;
+#pragma unroll
+            for (int j = 0; j < NA; ++j) z = z || CELL[j] == c;  // (REWARD | OBS: the cells marked by this launch)
+        }
+        const float v = samp_density(io, b, qx, qy) / mp;
+        o[4 + nr + i] = z ? 0.f : v;
+    }
+}
+
+#ifdef __HIP_DEVICE_COMPILE__
+typedef const VmasSamplingIO __attribute__((address_space(4))) KSamplingIO;  // (see k_flocking_fast)
+typedef const VmasSamplingMaxPdfIO __attribute__((address_space(4))) KSamplingMaxPdfIO;
+#else
+typedef const VmasSamplingIO KSamplingIO;
+typedef const VmasSamplingMaxPdfIO KSamplingMaxPdfIO;
+#endif
+
+// Grid: x = 64-env groups, y = groups of 4 agents; a wave per (64 envs, agent), the observation rows
+// staged in LDS (4 x 64 x W floats, sized by the launch) and written out as contiguous blocks, as
+// k_navigation_fast.  NA: the static bound of the agent loops (4, 8 or 16: the least >= n_agents).
+template <int NA>
+__global__ void __launch_bounds__(256) k_sampling(VmasSamplingIO io_arg) {
+#ifdef __HIP_DEVICE_COMPILE__
+    KSamplingIO& io = *(KSamplingIO*)__builtin_amdgcn_kernarg_segment_ptr();
+    (void)io_arg;
+#else
+    KSamplingIO& io = io_arg;
+#endif
+    extern __shared__ float samp_lds[];
+    const int lane = (int)(threadIdx.x & 63u), w = (int)(threadIdx.x >> 6);
+    const int g0 = (int)blockIdx.x * 64, b = g0 + lane;
+    const int k = __builtin_amdgcn_readfirstlane((int)blockIdx.y * 4 + w);
+    if (k >= io.n_agents) return;  // (wave-uniform; no workgroup barrier below)
+    const bool valid = b < io.batch;
+    const int nr = io.lidar_on ? io.n_rays : 0, W = 12 + nr;
+    float* S = samp_lds + w * 64 * W;
+    const OutDelta od = load_out_delta(io);
+    if (!(io.what & VMAS_SCN_OBS)) {
+        if (valid && k == 0) samp_agent<NA>(io, (long)b, 0, nullptr, nullptr, od.rew);
+        return;
+    }
+    if (valid) samp_agent<NA>(io, (long)b, k, S + lane * W, nullptr, od.rew);
+    __builtin_amdgcn_wave_barrier();
+    const int nv = io.batch - g0 < 64 ? io.batch - g0 : 64;
+    float* obs = moved(io.obs[k], od.obs) + (long)g0 * W;
+    for (int i = lane; i < nv * W; i += 64) obs[i] = S[i];
+    if (nr > 0) {
+        float* lid = io.lidar[k] + (long)g0 * nr;
+        for (int i = lane; i < nv * nr; i += 64) {
+            const int e = i / nr;
+            lid[i] = S[e * W + 4 + (i - e * nr)];
+        }
+    }
+}
+
+// nomrlize_pdf: a wave per env, lanes over the grid points, then the wave's maximum (order-free).
+__global__ void __launch_bounds__(256) k_sampling_max_pdf(VmasSamplingMaxPdfIO io_arg) {
+#ifdef __HIP_DEVICE_COMPILE__
+    KSamplingMaxPdfIO& io = *(KSamplingMaxPdfIO*)__builtin_amdgcn_kernarg_segment_ptr();
+    (void)io_arg;
+#else
+    KSamplingMaxPdfIO& io = io_arg;
+#endif
+    const int lane = (int)(threadIdx.x & 63u), w = (int)(threadIdx.x >> 6);
+    const int b = __builtin_amdgcn_readfirstlane((int)blockIdx.x * 4 + w);
+    if (b >= io.batch) return;
+    if (io.mask && !io.mask[b]) return;
+    const int ny = io.n_ys, P = io.n_xs * ny;
+    float m = 0.f;  // (max_pdf[:] = 0 before the loop)
+    for (int p = lane; p < P; p += 64) {
+        const int ix = p / ny, iy = p - ix * ny;
+        m = samp_max(m, samp_grid_point(io, (long)b, io.xs[ix], io.ys[iy]));
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) m = samp_max(m, __shfl_xor(m, off, 64));
+    if (lane == 0) io.max_pdf[b] = m;
+}
+
+const char* samp_density_error(const VmasSamplingGrid& g, const VmasSamplingDensity& d) {
+    if (g.n_x <= 0 || g.n_y <= 0 || (long)g.n_x * g.n_y > (1L << 30)) return "grid size";
+    if (g.div_mode != 0 && g.div_mode != 1) return "division mode";
+    if (d.n_gaussians < 1 || d.n_gaussians > VMAS_SAMPLING_MAX_GAUSSIANS) return "Gaussian count";
+    if (d.sum_mode < 1 || d.sum_mode > VMAS_SAMPLING_MAX_GAUSSIANS || (d.sum_mode & (d.sum_mode - 1))) return "sum mode";
+    for (int i = 0; i < d.n_gaussians; ++i)
+        if (!d.loc[i].p) return "null Gaussian location";
+    return nullptr;
+}
+
 // Test kernel (tests/test_fused.py test_exact_math_gpu): the flag-independent division / square
 // root of vmas_programs.hpp next to this translation unit's IEEE `/` and sqrtf.
 __global__ void k_test_exact_math(const float* a, const float* b, float* out, long n) {
@@ -1338,6 +1635,66 @@ int32_t vmas_navigation_outputs(int32_t device, const VmasNavigationIO* io, void
     bool pairs = false;  // (no pair passes the static part of World.collides: nothing to settle)
     for (int i = 0; i < n; ++i) pairs = pairs || io->pair_static[i] != 0u;
     if ((io->what & VMAS_SCN_REWARD) && pairs) hipLaunchKernelGGL(k_navigation_pairs, dim3(1), dim3(1024), 0, st, *io);
+    VMAS_AUX_HIP(hipGetLastError());
+    return VMAS_OK;
+}
+
+int32_t vmas_sampling_outputs(int32_t device, const VmasSamplingIO* io, void* stream) {
+    if (!io || device >= 64 || io->batch <= 0 || io->n_agents < 1 || io->n_agents > VMAS_SAMPLING_MAX_AGENTS ||
+        io->n_rays < 0 || io->n_rays > VMAS_SAMPLING_MAX_RAYS || !(io->what & (VMAS_SCN_REWARD | VMAS_SCN_OBS)) ||
+        io->agent_sum_mode < 1 || io->agent_sum_mode > VMAS_SAMPLING_MAX_AGENTS ||
+        (io->agent_sum_mode & (io->agent_sum_mode - 1)) || !io->max_pdf || !io->sampled)
+        return vmas_aux::fail(VMAS_E_INVALID, "vmas_sampling_outputs: bad arguments");
+    if (const char* why = samp_density_error(io->grid, io->density))
+        return vmas_aux::fail(VMAS_E_INVALID, "vmas_sampling_outputs: bad arguments (%s)", why);
+    const int n = io->n_agents, nr = io->lidar_on ? io->n_rays : 0;
+    for (int i = 0; i < n; ++i) {
+        bool ok = io->pos[i].p != nullptr;
+        if (io->what & VMAS_SCN_REWARD) ok = ok && io->sample[i] && io->rewards[i] && io->sampling_rew;
+        if (io->what & VMAS_SCN_OBS) ok = ok && io->vel[i].p && io->obs[i] && (nr == 0 || (io->rot[i].p && io->angles[i] && io->lidar[i]));
+        if (!ok) return vmas_aux::fail(VMAS_E_INVALID, "vmas_sampling_outputs: null pointer (agent %d)", i);
+    }
+    const int W = 12 + nr;
+    if (device < 0) {
+        if (io->out_delta) return vmas_aux::fail(VMAS_E_INVALID, "vmas_sampling_outputs: out_delta on the host");
+        for (long b = 0; b < io->batch; ++b)
+            for (int k = 0; k < n; ++k) {
+                const bool obs = (io->what & VMAS_SCN_OBS) != 0;
+                if (!obs && k > 0) break;
+                samp_agent<kSampMA>(*io, b, k, obs ? io->obs[k] + b * W : nullptr, (obs && nr > 0) ? io->lidar[k] + b * nr : nullptr, 0);
+            }
+        return VMAS_OK;
+    }
+    VMAS_AUX_HIP(hipSetDevice(device));
+    static_assert(sizeof(VmasSamplingIO) <= 4096, "kernel argument block");
+    const hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((io->batch + 63) / 64, ((io->what & VMAS_SCN_OBS) ? n + 3 : 4) / 4);
+    const size_t lds = (size_t)4 * 64 * W * sizeof(float);
+    if (n <= 4) hipLaunchKernelGGL((k_sampling<4>), grid, dim3(256), lds, st, *io);
+    else if (n <= 8) hipLaunchKernelGGL((k_sampling<8>), grid, dim3(256), lds, st, *io);
+    else hipLaunchKernelGGL((k_sampling<16>), grid, dim3(256), lds, st, *io);
+    VMAS_AUX_HIP(hipGetLastError());
+    return VMAS_OK;
+}
+
+int32_t vmas_sampling_max_pdf(int32_t device, const VmasSamplingMaxPdfIO* io, void* stream) {
+    if (!io || device >= 64 || io->batch <= 0 || io->n_xs <= 0 || io->n_ys <= 0 || (long)io->n_xs * io->n_ys > (1L << 30) ||
+        !io->xs || !io->ys || !io->max_pdf)
+        return vmas_aux::fail(VMAS_E_INVALID, "vmas_sampling_max_pdf: bad arguments");
+    if (const char* why = samp_density_error(io->grid, io->density))
+        return vmas_aux::fail(VMAS_E_INVALID, "vmas_sampling_max_pdf: bad arguments (%s)", why);
+    if (device < 0) {
+        for (long b = 0; b < io->batch; ++b) {
+            if (io->mask && !io->mask[b]) continue;
+            float m = 0.f;
+            for (int ix = 0; ix < io->n_xs; ++ix)
+                for (int iy = 0; iy < io->n_ys; ++iy) m = samp_max(m, samp_grid_point(*io, b, io->xs[ix], io->ys[iy]));
+            io->max_pdf[b] = m;
+        }
+        return VMAS_OK;
+    }
+    VMAS_AUX_HIP(hipSetDevice(device));
+    hipLaunchKernelGGL(k_sampling_max_pdf, dim3((io->batch + 3) / 4), dim3(256), 0, (hipStream_t)stream, *io);
     VMAS_AUX_HIP(hipGetLastError());
     return VMAS_OK;
 }

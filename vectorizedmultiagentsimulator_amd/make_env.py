@@ -35,8 +35,11 @@ def make_env(
     kernels).  ``scenario`` is a scenario file name from ``scenarios/`` or a BaseScenario.
     ``graph_step`` (not in the reference): True replays each step as one HIP graph once the world
     is warm, with the same results (ROCm devices; simulator/environment/_graph.py); False keeps
-    the eager step; None (default) picks the graph where it is known to be exact -- a ROCm device,
-    continuous actions, no autograd, one of this package's scenarios (Environment._auto_graph_step).
+    the eager step; None (default) asks for the graph on a ROCm device without autograd, for any
+    scenario and for continuous and discrete actions alike: the step is captured only after a
+    watched eager step proves it capturable, otherwise the env stays eager and ``graph_status`` /
+    ``graph_reason`` say why (Environment._auto_graph_step; VMAS_GRAPH_STEP=0 turns the choice off,
+    VMAS_GRAPH_STEP=own keeps it to this package's scenarios).
     """
     if isinstance(scenario, str):
         if not scenario.endswith(".py"):

@@ -96,24 +96,26 @@ def bump_version(t: torch.Tensor) -> None:
 _ORDER_CACHE = {}
 
 
-def reduce_order(dev: torch.device, n: int):
-    """The summation order of torch's .mean(-1) over a contiguous [B, n] fp32 tensor on this
+def reduce_order(dev: torch.device, n: int, op: str = "mean", cap: int = None):
+    """The summation order of torch's .mean(-1) (``op`` "sum": .sum(-1), probed on its own; ``cap``:
+    the largest accumulator count the asking kernel takes, default flocking's) over a contiguous
+    [B, n] fp32 tensor on this
     device, as the accumulator count of the fused kernels' ordered_sum (vmas_scenarios.hip):
     acc strided accumulators combined by an adjacent-pair tree.  Probed once per (device, n)
     against torch itself on random values of mixed magnitude (tools/probe_mean_order.py: on
     MI355X / ROCm 7.2 the largest power of two <= n); None if no count reproduces it bit for
     bit (the scenario then keeps its torch program)."""
-    key = (str(dev), n)
+    key = (str(dev), n) if op == "mean" else (str(dev), n, op)
     if key in _ORDER_CACHE:
         return _ORDER_CACHE[key]
     g = torch.Generator(device="cpu").manual_seed(1234 + n)
     x = (torch.rand(4096, n, generator=g) * torch.exp2(torch.randint(-12, 12, (4096, n), generator=g).float()))
     x = x.to(dev).contiguous()
-    ref = x.mean(-1)
+    ref = x.mean(-1) if op == "mean" else x.sum(-1)
     cols = [x[:, i] for i in range(n)]
     found = None
     acc = 1
-    while acc <= min(n, N.VMAS_FLOCK_MAX_AGENTS):
+    while acc <= min(n, cap or N.VMAS_FLOCK_MAX_AGENTS):
         y = []
         for i in range(acc):
             a = cols[i]
@@ -125,7 +127,7 @@ def reduce_order(dev: torch.device, n: int):
             for i in range(0, len(y) - w, 2 * w):
                 y[i] = y[i] + y[i + w]
             w *= 2
-        if torch.equal(y[0] * (1.0 / n), ref):
+        if torch.equal(y[0] * (1.0 / n) if op == "mean" else y[0], ref):
             found = acc
             break
         acc *= 2

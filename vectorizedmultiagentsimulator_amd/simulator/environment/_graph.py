@@ -133,9 +133,10 @@ _STEP_METHODS = ("reward", "observation", "done", "info", "pre_step", "post_step
 
 # The scenarios whose step code the replay trusts beyond the watched eager step (write-only
 # attributes, direct outputs): the four benchmark scenarios, each held to its eager step by
-# tests/test_graph.py, and navigation, held to it by tests/test_navigation_gpu.py (not
+# tests/test_graph.py, navigation, held to it by tests/test_navigation_gpu.py, and sampling, held to
+# it by tests/test_sampling_gpu.py (not
 # every file of the scenarios directory -- the debug scenarios are replayed like a user's scenario).
-_TRUSTED_FILES = ("balance.py", "transport.py", "discovery.py", "flocking.py", "navigation.py")
+_TRUSTED_FILES = ("balance.py", "transport.py", "discovery.py", "flocking.py", "navigation.py", "sampling.py")
 
 
 def _trusted_scenario(scenario) -> bool:
@@ -697,6 +698,7 @@ class StepGraph:
         self._first_replay = True
         self._asserts: Optional[_DeviceAsserts] = None
         self._inplace: List[Tensor] = []
+        self._restorers: List[Any] = []  # (a trusted scenario's own undo functions: _capture)
         self._write_only_ys: List[Tensor] = []  # (re-bound, not carried: _write_only)
         self._bk_src: List[Tensor] = []
         self._bk_dst: List[Tensor] = []
@@ -1024,7 +1026,17 @@ class StepGraph:
                 self._direct.finalize(_tensors(out, []), env.scenario)
             out_tensors = self._plan(objs, snap, out)
             self._direct.arm(N.stream_ptr(self._dev_index()))
-            self._inplace = [t for t, v in versions.values() if t._version != v]
+            # a trusted scenario may undo its own in-place writes (`_vmas_graph_restorers`: attribute
+            # name -> a function that takes the last step's writes back, e.g. sampling's 52 MB of
+            # visited-cell flags from the few cells the step marked): no per-step backup of those
+            self._restorers, own_undo = [], set()
+            scn = env.scenario
+            if _trusted_scenario(scn) and hasattr(type(scn), "_vmas_graph_restorers"):
+                for k, fn in scn._vmas_graph_restorers().items():
+                    if isinstance(scn.__dict__.get(k), Tensor):
+                        own_undo.add(id(scn.__dict__[k]))
+                        self._restorers.append(fn)
+            self._inplace = [t for t, v in versions.values() if t._version != v and id(t) not in own_undo]
             ids = {id(t) for t in self._inplace}
             self._inplace += [y for y in self._write_only_ys if id(y) not in ids]
             self._bk_src, self._bk_dst, self._bk_u = [], [], None
@@ -1388,6 +1400,8 @@ class StepGraph:
                 torch._foreach_copy_(self._carry_src, self._carry_dst)
             for x, y in self._carry_other:
                 y.copy_(x)
+            for fn in self._restorers:  # (the scenario's own undo of its in-place writes)
+                fn()
         torch.cuda.set_rng_state(rng, self.env.device)
 
     def _dev_index(self) -> int:
