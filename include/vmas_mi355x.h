@@ -51,8 +51,9 @@ extern "C" {
  * v10: VmasNavigationIO / vmas_navigation_outputs
  * v11: VmasTransportIO rew_attr
  * v12: VmasActionProgramRef / vmas_action_programs, VmasVelocityPidRef / vmas_velocity_pid
- * v13: VmasSamplingIO / vmas_sampling_outputs, VmasSamplingMaxPdfIO / vmas_sampling_max_pdf */
-#define VMAS_ABI_VERSION 13
+ * v13: VmasSamplingIO / vmas_sampling_outputs, VmasSamplingMaxPdfIO / vmas_sampling_max_pdf
+ * v14: VmasResetDerived / VmasSpawnResetIO / vmas_spawn_reset */
+#define VMAS_ABI_VERSION 14
 
 /* error codes */
 #define VMAS_OK 0
@@ -1208,6 +1209,69 @@ typedef struct VmasBalanceResetIO {
     float* steps;              /* [B] contiguous, or NULL */
 } VmasBalanceResetIO;
 int32_t vmas_balance_reset(int32_t device, const VmasBalanceResetIO* io, uint64_t* increment, void* stream);
+
+/* vmas_spawn_reset (v14) <- the reset of a scenario whose reset_world_at(None) is a chain of
+ * ScenarioUtils.spawn_entities_randomly / find_random_pos_for_entity placements
+ * (vmas/simulator/utils.py:239-319; navigation.py, transport.py, discovery.py `reset_world_at`) after
+ * World.reset, for the rows of a mask, in place.
+ *
+ * Placement (every env, whatever the mask: an env outside it can hold the batch's largest try count):
+ * entity i = 0 .. n_place-1 takes, per env, its first try k whose candidate lies at d2 >= d2_min of
+ * every fixed position and of every entity placed before it (d2 = fl(fl(d0^2) + fl(d1^2)), d2_min =
+ * the smallest float whose sqrtf reaches min_dist[i]: torch.cdist(...) < min_dist without the sqrt).
+ * Try k of entity i is pair P_i + k of ONE stream of uniform_ calls on B elements: x at generator
+ * offset `offset` + (P_i + k) * per_try over [x_lo, x_hi), y one call later over [y_lo, y_hi)
+ * (per_try = two calls; mode as vmas_uniform_columns).  P_0 = 0, P_{i+1} = P_i + consumed_i, consumed_i
+ * = 1 if the largest accepted k over the batch is 0, else that k + 2 (the reference loop's tries).
+ * One launch per entity (the kernel boundary is the batch-wide hand-off: nothing waits inside a
+ * kernel); accepted candidates go to scratch[slot i][2][B], the per-entity maxima to words[i], the
+ * envs that found nothing in max_tries tries (<= 0: VMAS_RESET_TRIES_LIMIT) are counted in
+ * words[VMAS_RESET_MAX_PLACE].
+ *
+ * Commit (one launch): nothing at all when an env was unresolved; else, for every env of the mask,
+ * entity w of `write` gets pos = the candidate of slot write_slot[w] and zero vel / rot / ang_vel,
+ * force[a] / torque[a] get zeros, steps[b] = 0, and every VmasResetDerived record is evaluated with
+ * the fused step programs' arithmetic (csrc/vmas_programs.hpp).
+ *
+ * The call then copies the words to the host and waits for the stream once.  *increment: what the
+ * full reset advances the generator by (the caller adds it, unless *unresolved != 0: then nothing
+ * was written and the caller redoes the reset another way from the same generator state). */
+#define VMAS_RESET_MAX_PLACE 16   /* entities placed by one call */
+#define VMAS_RESET_MAX_WRITE 24   /* entities written by one call */
+#define VMAS_RESET_MAX_AGENTS 16  /* force / torque pairs */
+#define VMAS_RESET_MAX_FIXED 8    /* fixed occupied positions */
+#define VMAS_RESET_MAX_DERIVED 16
+#define VMAS_RESET_WORDS 32       /* int32 words: [0, n_place) maxima, [VMAS_RESET_MAX_PLACE] unresolved envs */
+#define VMAS_RESET_TRIES_LIMIT 16384
+#define VMAS_RESET_D_NORM 1       /* out[b] = |slot a - slot b| * factor (torch.linalg.vector_norm, dim 2) */
+#define VMAS_RESET_D_BOX_SPHERE 2 /* out8[b] = is_overlapping(box length x width at slot a, rot 0; sphere at slot b) */
+#define VMAS_RESET_D_CLEAR8 3     /* out8[b * n .. + n) = 0 */
+typedef struct VmasResetDerived {
+    int32_t kind, a, b, n; /* VMAS_RESET_D_*; scratch slots; CLEAR8: bytes per row */
+    float factor;          /* NORM */
+    float length, width;   /* BOX_SPHERE: f32 of the box's sizes */
+    float radius_lmd;      /* BOX_SPHERE: the sphere's VmasShapeRef.radius_lmd */
+    VmasMutVec out;        /* NORM: [B] */
+    uint8_t* out8;         /* BOX_SPHERE: [B] torch.bool contiguous; CLEAR8: [B, n] contiguous */
+} VmasResetDerived;
+typedef struct VmasSpawnResetIO {
+    int32_t batch, mode, max_tries, n_place;
+    int32_t n_fixed, n_write, n_agents, n_derived;
+    uint64_t seed, offset;
+    float x_lo, x_hi, y_lo, y_hi;        /* f32 of the bounds every placement shares */
+    float min_dist[VMAS_RESET_MAX_PLACE]; /* f32(min_dist_between_entities) of entity i's spawn call */
+    const uint8_t* mask;                  /* [B] torch.bool */
+    float* scratch;                       /* >= n_place * 2 * B floats */
+    int32_t* words;                       /* VMAS_RESET_WORDS int32 (zeroed by the call's first kernel) */
+    float* steps;                         /* [B] contiguous, or NULL */
+    VmasVec fixed[VMAS_RESET_MAX_FIXED];  /* [B, 2]: occupied before the first placement */
+    int32_t write_slot[VMAS_RESET_MAX_WRITE];
+    VmasResetEntity write[VMAS_RESET_MAX_WRITE];
+    VmasMutVec force[VMAS_RESET_MAX_AGENTS], torque[VMAS_RESET_MAX_AGENTS];
+    VmasResetDerived derived[VMAS_RESET_MAX_DERIVED];
+} VmasSpawnResetIO;
+int32_t vmas_spawn_reset(int32_t device, const VmasSpawnResetIO* io, uint64_t* increment, int32_t* unresolved,
+                         void* stream);
 
 /* ---- sampling (v13; reference vmas/scenarios/sampling.py `sample`, `reward`, `observation`,
  * `nomrlize_pdf`; restated in scenarios/sampling.py) ------------------------------------------------

@@ -19,6 +19,17 @@ A tree without ``reset_where`` (the parent commit) times only reset and reset_at
                                 [--methods reset,reset_at_loop,where_generic,where_native]
 
 Writes profiles/r12/masked_reset/<label>.json and prints the same JSON line.
+
+``--scenario NAME[,NAME...]`` (balance, navigation, transport, discovery) times those scenarios
+instead, ``where_native`` for every one whose class has a ``reset_world_where`` of its own
+(navigation, transport, discovery: vmas_spawn_reset), and writes under profiles/r16/spawn_reset.
+``--package-root DIR`` imports the package from DIR, a built checkout of another commit (the parent:
+its ``reset_where`` is the generic path, ``where_generic``), so that the two trees can be run
+alternately on the same calls:
+
+    python tools/reset_bench.py --scenario navigation,transport,discovery --methods reset,where_generic,where_native
+    python tools/reset_bench.py --scenario navigation,transport,discovery --methods reset,where_generic \
+                                --package-root ../parent --label parent
 """
 import argparse
 import json
@@ -32,6 +43,13 @@ sys.path.insert(0, str(ROOT))
 WORKLOADS = {
     "balance": dict(envs=32768, kw=dict(n_agents=4), substeps=10),   # C2
     "transport": dict(envs=32768, kw=dict(n_agents=4), substeps=0),  # C3
+}
+# --scenario: the scenarios with a native reset_where, at the sizes of their step benchmarks
+SCENARIOS = {
+    "balance": WORKLOADS["balance"],
+    "navigation": dict(envs=32768, kw=dict(n_agents=4), substeps=0),
+    "transport": WORKLOADS["transport"],
+    "discovery": dict(envs=16384, kw=dict(), substeps=0),  # C4
 }
 DENSITIES = (0.01, 0.1, 1.0)
 
@@ -53,7 +71,7 @@ def run(args, name):
 
     from vectorizedmultiagentsimulator_amd import make_env
 
-    wl = WORKLOADS[name]
+    wl = SCENARIOS[name] if args.scenario else WORKLOADS[name]
     B = wl["envs"]
     env = make_env(name, num_envs=B, device=args.device, seed=0, **wl["kw"])
     if wl["substeps"]:
@@ -63,6 +81,10 @@ def run(args, name):
     for _ in range(args.warmup):
         step()
     has_where = hasattr(env, "reset_where")
+    from vectorizedmultiagentsimulator_amd.simulator.scenario import BaseScenario
+
+    # the scenario resets the rows of a mask itself (k_balance_reset, vmas_spawn_reset)
+    own = getattr(type(env.scenario), "reset_world_where", None) is not getattr(BaseScenario, "reset_world_where", None)
     out = {"envs": B, "graph_status": getattr(env, "graph_status", "off"), "has_reset_where": has_where}
     out["step_us"] = round(timed(torch, step, args.reps)[0], 2)
     g = torch.Generator(device="cpu").manual_seed(0)
@@ -88,7 +110,7 @@ def run(args, name):
             methods["reset_at_loop"] = (loop, n / len(sub))
         if has_where and "where_generic" in args.methods:
             def generic():
-                if name == "balance":  # (the scenario's own reset declines for the call: an instance attribute)
+                if own:  # (the scenario's own reset declines for the call: an instance attribute)
                     env.scenario.reset_world_where = lambda m: NotImplemented
                 try:
                     env.reset_where(mask)
@@ -96,7 +118,7 @@ def run(args, name):
                     env.scenario.__dict__.pop("reset_world_where", None)
 
             methods["where_generic"] = (generic, 1.0)
-        if has_where and name == "balance" and "where_native" in args.methods:
+        if has_where and own and (name == "balance" or args.scenario) and "where_native" in args.methods:
             methods["where_native"] = (lambda: env.reset_where(mask), 1.0)
         for m, (fn, scale) in methods.items():
             reps = 2 if m == "reset_at_loop" else args.reps
@@ -121,12 +143,21 @@ def main():
     p.add_argument("--warmup", type=int, default=20)
     p.add_argument("--cap", type=int, default=200, help="most indices the reset_at loop is timed over")
     p.add_argument("--only", default=None, choices=list(WORKLOADS))
+    p.add_argument("--scenario", default=None, help="comma-separated: " + ", ".join(SCENARIOS))
+    p.add_argument("--package-root", default="", help="a built tree of another commit to import the package from")
     p.add_argument("--methods", default="reset,reset_at_loop,where_generic,where_native")
     p.add_argument("--device", default="cuda:0")
     p.add_argument("--label", default="run")
     p.add_argument("--out", default=None, help="directory of the JSON (default profiles/r12/masked_reset)")
     args = p.parse_args()
     args.methods = args.methods.split(",")
+    if args.scenario:
+        args.scenario = args.scenario.split(",")
+        for name in args.scenario:
+            if name not in SCENARIOS:
+                p.error(f"--scenario {name}: one of {', '.join(SCENARIOS)}")
+    if args.package_root:
+        sys.path.insert(0, str(Path(args.package_root).resolve()))
     import torch
 
     if not torch.cuda.is_available():
@@ -134,9 +165,12 @@ def main():
     out = {"bench": "masked_reset", "label": args.label, "reps": args.reps, "warmup": args.warmup,
            "reset_at_cap": args.cap,
            "note": f"reset_at_loop: timed over at most {args.cap} indices and scaled to the mask's count"}
-    for name in ([args.only] if args.only else list(WORKLOADS)):
+    if args.package_root:
+        out["package_root"] = args.package_root
+    for name in (args.scenario or ([args.only] if args.only else list(WORKLOADS))):
         out[name] = run(args, name)
-    d = Path(args.out) if args.out else ROOT / "profiles" / "r12" / "masked_reset"
+    sub = ("r16", "spawn_reset") if args.scenario else ("r12", "masked_reset")
+    d = Path(args.out) if args.out else ROOT / "profiles" / sub[0] / sub[1]
     d.mkdir(parents=True, exist_ok=True)
     (d / f"{args.label}.json").write_text(json.dumps(out, indent=1) + "\n")
     print(json.dumps(out), flush=True)

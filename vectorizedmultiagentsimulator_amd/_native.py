@@ -19,7 +19,7 @@ LIB_PATH = Path(os.environ.get("VMAS_LIB_PATH") or Path(__file__).resolve().pare
 
 # ------------------------------------------------------------------------------------------------
 # constants mirrored from include/vmas_mi355x.h
-VMAS_ABI_VERSION = 13
+VMAS_ABI_VERSION = 14
 VMAS_SPHERE, VMAS_BOX, VMAS_LINE = 0, 1, 2
 (
     VMAS_PAIR_JOINT,
@@ -132,6 +132,7 @@ EXPORTED_SYMBOLS = (
     "vmas_render_scene",
     "vmas_masked_rows",
     "vmas_balance_reset",
+    "vmas_spawn_reset",
     "vmas_action_programs",
     "vmas_velocity_pid",
 )
@@ -464,6 +465,38 @@ class VmasBalanceResetIO(ctypes.Structure):
         ("agents", VmasResetEntity * VMAS_SCN_MAX_AGENTS),
         ("force", VmasMutVec * VMAS_SCN_MAX_AGENTS), ("torque", VmasMutVec * VMAS_SCN_MAX_AGENTS),
         ("on_the_ground", _vp), ("global_shaping", VmasMutVec), ("steps", _vp),
+    ]
+
+
+# the spawn reset (csrc/vmas_reset.hip k_reset_place / k_reset_commit; simulator/environment/_spawn_reset.py)
+VMAS_RESET_MAX_PLACE = 16
+VMAS_RESET_MAX_WRITE = 24
+VMAS_RESET_MAX_AGENTS = 16
+VMAS_RESET_MAX_FIXED = 8
+VMAS_RESET_MAX_DERIVED = 16
+VMAS_RESET_WORDS = 32
+VMAS_RESET_TRIES_LIMIT = 16384
+VMAS_RESET_D_NORM, VMAS_RESET_D_BOX_SPHERE, VMAS_RESET_D_CLEAR8 = 1, 2, 3
+
+
+class VmasResetDerived(ctypes.Structure):
+    _fields_ = [("kind", _i32), ("a", _i32), ("b", _i32), ("n", _i32), ("factor", _f32), ("length", _f32),
+                ("width", _f32), ("radius_lmd", _f32), ("out", VmasMutVec), ("out8", _vp)]
+
+
+class VmasSpawnResetIO(ctypes.Structure):
+    _fields_ = [
+        ("batch", _i32), ("mode", _i32), ("max_tries", _i32), ("n_place", _i32),
+        ("n_fixed", _i32), ("n_write", _i32), ("n_agents", _i32), ("n_derived", _i32),
+        ("seed", ctypes.c_uint64), ("offset", ctypes.c_uint64),
+        ("x_lo", _f32), ("x_hi", _f32), ("y_lo", _f32), ("y_hi", _f32),
+        ("min_dist", _f32 * VMAS_RESET_MAX_PLACE),
+        ("mask", _vp), ("scratch", _vp), ("words", _vp), ("steps", _vp),
+        ("fixed", VmasVec * VMAS_RESET_MAX_FIXED),
+        ("write_slot", _i32 * VMAS_RESET_MAX_WRITE),
+        ("write", VmasResetEntity * VMAS_RESET_MAX_WRITE),
+        ("force", VmasMutVec * VMAS_RESET_MAX_AGENTS), ("torque", VmasMutVec * VMAS_RESET_MAX_AGENTS),
+        ("derived", VmasResetDerived * VMAS_RESET_MAX_DERIVED),
     ]
 
 
@@ -819,6 +852,8 @@ def load_library(path: os.PathLike | str | None = None) -> ctypes.CDLL:
     lib.vmas_masked_rows.argtypes = [_i32, _vp, _i32, _vp, ctypes.c_int64, _i32, _vp]
     lib.vmas_balance_reset.restype = _i32
     lib.vmas_balance_reset.argtypes = [_i32, _vp, ctypes.POINTER(ctypes.c_uint64), _vp]
+    lib.vmas_spawn_reset.restype = _i32
+    lib.vmas_spawn_reset.argtypes = [_i32, _vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(_i32), _vp]
     lib.vmas_stream_abort_capture.restype = _i32
     lib.vmas_stream_abort_capture.argtypes = [_vp]
     lib.vmas_graph_launch.restype = _i32

@@ -5,7 +5,9 @@
 
 #include <hip/hip_runtime.h>
 
+#include <math.h>
 #include <stdint.h>
+#include <string.h>
 
 namespace vmas_aux {
 
@@ -30,6 +32,24 @@ int32_t wait_host_word64(const uint64_t* word, uint32_t seq, uint64_t* value, hi
 // found not complete before the next kernel, and words left holding pointer-like data), while a
 // kernel node is ordered and parameterised like every other node of the graph.
 hipError_t fill_u32_async(void* dst, uint32_t value, size_t n_words, hipStream_t stream);
+
+// The smallest float x >= 0 with sqrtf(x) >= min_dist (binary search over the ordered bit patterns
+// of non-negative floats; sqrtf is correctly rounded on the host as on the device):
+// torch.cdist(...) < min_dist is d2 < spawn_d2_min(min_dist) without the square root.
+inline float spawn_d2_min(float min_dist) {
+    if (!(min_dist > 0.f)) return 0.f;  // sqrt(d2) < min_dist never holds: neither does d2 < 0
+    uint32_t lo = 0u, hi = 0x7f800000u;  // sqrtf(+inf) = inf >= min_dist
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo) / 2u;
+        float x;
+        memcpy(&x, &mid, 4);
+        if (sqrtf(x) >= min_dist) hi = mid;
+        else lo = mid + 1u;
+    }
+    float r;
+    memcpy(&r, &lo, 4);
+    return r;
+}
 
 }  // namespace vmas_aux
 

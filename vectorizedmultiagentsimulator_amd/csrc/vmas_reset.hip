@@ -8,9 +8,14 @@
 // row b), places the entities with the reference's fp32 additions (-ffp-contract=off: no FMA), and
 // computes on_the_ground / global_shaping with the functions of the fused step program
 // (vmas_programs.hpp), which equal the torch program bit for bit (tests/test_fused.py).
+//
+// k_reset_place / k_reset_commit (vmas_spawn_reset): the reset of a scenario that places its entities
+// by rejection sampling (utils.py:239-319 spawn_entities_randomly / find_random_pos_for_entity), see
+// the second half of this file.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <mutex>
 
 #include "vmas_aux.hpp"
 #include "vmas_mi355x.h"
@@ -110,6 +115,130 @@ __global__ void __launch_bounds__(kResetThreads) k_balance_reset(VmasBalanceRese
     if (io.steps) io.steps[b] = 0.f;
 }
 
+// ---- the spawn reset (vmas_spawn_reset) ------------------------------------------------------------
+// The reference's placement loop (vmas_spawn.hip's head states it): per entity, every env keeps its
+// FIRST candidate that overlaps nothing, and the loop consumes 1 try if every env accepts candidate 0,
+// else (the largest accepted index over the batch) + 2.  The next entity's tries start where these end,
+// so its candidates depend on a maximum over ALL envs: the hand-off between two entities is batch-wide.
+// Here it is the kernel boundary -- one k_reset_place launch per entity, queued back to back by one
+// call, no wait between workgroups inside a kernel and nothing that can spin.  Launch i reads the
+// maxima of entities 0 .. i-1 (complete: their kernels have ended), draws its own tries with
+// uniform_at (the numbers the torch uniform_ calls of the full reset produce), tests them against the
+// fixed positions and the accepted candidates of the entities before it, and publishes its own
+// maximum with one agent-scope atomicMax per wave.  The placement kernels write scratch and the words
+// only; k_reset_commit then writes the world, for the envs of the mask, and only when every env of
+// the batch found a place (else the caller redoes the reset another way: nothing was written).
+struct PlaceArgs {
+    int32_t batch, index, n_fixed, max_tries, mode, pad0;
+    float d2_min, x_lo, x_hi, y_lo, y_hi, pad1;
+    unsigned long long seed, offset;
+    float* scratch;  // [slot][2][B]: slot i's x row, then its y row (a wave reads consecutive floats)
+    int32_t* words;  // [0, n_place) the maxima, [VMAS_RESET_MAX_PLACE] unresolved envs
+    VmasVec fixed[VMAS_RESET_MAX_FIXED];
+};
+static_assert(sizeof(PlaceArgs) + sizeof(vmas_uniform::DrawGrid) <= 4096, "kernel argument block");
+static_assert(sizeof(VmasSpawnResetIO) <= 4096, "kernel argument block");
+static_assert(VMAS_RESET_MAX_PLACE < VMAS_RESET_WORDS, "the unresolved word");
+
+// torch.cdist(...) < min_dist as d2 < d2_min (vmas_spawn.hip near; vmas_aux.hpp spawn_d2_min)
+__device__ __forceinline__ bool too_near(float ox, float oy, float x, float y, float d2_min) {
+    const float d0 = ox - x, d1 = oy - y;
+    return d0 * d0 + d1 * d1 < d2_min;
+}
+
+__global__ void __launch_bounds__(kResetThreads) k_reset_place(PlaceArgs a_arg, vmas_uniform::DrawGrid g) {
+    VMAS_PROGRAM_ARGS(PlaceArgs, a_arg);
+    const int B = io.batch, i = io.index;
+    int32_t* W = io.words;
+    // an earlier entity left an env without a place: the call is void, skip the work.  (Envs of THIS
+    // launch add to the word too; a workgroup that sees them skips work that is void all the same.)
+    if (__hip_atomic_load(W + VMAS_RESET_MAX_PLACE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) return;
+    const int b = blockIdx.x * kResetThreads + threadIdx.x;
+    unsigned long long first = 0;  // P_i: the tries the entities before this one consumed
+    for (int j = 0; j < i; ++j) {
+        const int m = W[j];
+        first += (unsigned long long)(m == 0 ? 1 : m + 2);
+    }
+    int accepted = 0, lost = 0;
+    if (b < B) {
+        float* S = io.scratch;
+        const int lim = io.max_tries, nf = io.n_fixed, mode = io.mode;
+        const float d2 = io.d2_min, x_lo = io.x_lo, x_hi = io.x_hi, y_lo = io.y_lo, y_hi = io.y_hi;
+        const unsigned long long seed = io.seed, per_try = 2ull * g.inc;
+        float x = 0.f, y = 0.f;
+        int k = 0;
+        for (;; ++k) {
+            if (k >= lim) {
+                lost = 1;
+                break;
+            }
+            const unsigned long long off = io.offset + (first + (unsigned long long)k) * per_try;
+            x = vmas_uniform::uniform_at(seed, off, g, b, x_lo, x_hi, mode);
+            y = vmas_uniform::uniform_at(seed, off + g.inc, g, b, y_lo, y_hi, mode);
+            bool hit = false;
+            for (int j = 0; j < nf; ++j) {
+                const VmasVec v = io.fixed[j];
+                const float* p = v.p + (long)b * v.s0;
+                hit = hit || too_near(p[0], p[v.s1], x, y, d2);
+            }
+            for (int j = 0; j < i; ++j)
+                hit = hit || too_near(S[(size_t)(2 * j) * B + b], S[(size_t)(2 * j + 1) * B + b], x, y, d2);
+            if (!hit) break;
+        }
+        if (!lost) {
+            S[(size_t)(2 * i) * B + b] = x;
+            S[(size_t)(2 * i + 1) * B + b] = y;
+            accepted = k;
+        }
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        accepted = max(accepted, __shfl_xor(accepted, off));
+        lost += __shfl_xor(lost, off);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (accepted > 0) atomicMax(W + i, accepted);
+        if (lost) atomicAdd(W + VMAS_RESET_MAX_PLACE, lost);
+    }
+}
+
+__global__ void __launch_bounds__(kResetThreads) k_reset_commit(VmasSpawnResetIO io_arg) {
+    VMAS_PROGRAM_ARGS(VmasSpawnResetIO, io_arg);
+    const int b = blockIdx.x * kResetThreads + threadIdx.x;
+    const int B = io.batch;
+    if (b >= B || io.mask[b] == 0) return;
+    if (io.words[VMAS_RESET_MAX_PLACE] != 0) return;  // (nothing has been written: the placement wrote scratch only)
+    const float* S = io.scratch;
+    auto slot = [&](int s) { return mk(S[(size_t)(2 * s) * B + b], S[(size_t)(2 * s + 1) * B + b]); };
+    for (int w = 0; w < io.n_write; ++w) {
+        const VmasResetEntity e = io.write[w];
+        place(e, b, slot(io.write_slot[w]));
+    }
+    for (int a = 0; a < io.n_agents; ++a) {
+        const VmasMutVec f = io.force[a], t = io.torque[a];
+        put2(f, b, 0.f, 0.f);
+        put1(t, b, 0.f);
+    }
+    if (io.steps) io.steps[b] = 0.f;
+    for (int d = 0; d < io.n_derived; ++d) {
+        const VmasResetDerived r = io.derived[d];
+        if (r.kind == VMAS_RESET_D_NORM) {
+            // vector_norm(pos_a - pos_b, dim=1) * factor, as the fused programs compute it
+            put1(r.out, b, xnorm(slot(r.a) - slot(r.b)) * r.factor);
+        } else if (r.kind == VMAS_RESET_D_BOX_SPHERE) {
+            // xoverlap_box_sphere (core.py:1932-1963) on the new positions; every rot is 0 after the reset
+            const V2 pb = slot(r.a), ps = slot(r.b);
+            const V2 cp = xclosest_point_box(pb, xtrig(0.f), r.length * 0.5f, r.width * 0.5f, ps);
+            const float dsc = xnorm(ps - cp), dsb = xnorm(ps - pb), dcb = xnorm(pb - cp);
+            r.out8[b] = ((dsb < dcb) || (dsc < r.radius_lmd)) ? 1 : 0;
+        } else if (r.kind == VMAS_RESET_D_CLEAR8) {
+            for (int k = 0; k < r.n; ++k) r.out8[(size_t)b * r.n + k] = 0;
+        }
+    }
+}
+
+std::mutex g_reset_mu;
+int32_t* g_reset_host_words[64] = {nullptr};  // pinned: the words of the last call, per device
+
 }  // namespace
 
 extern "C" int32_t vmas_balance_reset(int32_t device, const VmasBalanceResetIO* io, uint64_t* increment, void* stream) {
@@ -134,5 +263,78 @@ extern "C" int32_t vmas_balance_reset(int32_t device, const VmasBalanceResetIO* 
     hipLaunchKernelGGL(k_balance_reset, dim3(gx), dim3(kResetThreads), 0, (hipStream_t)stream, *io, g);
     VMAS_AUX_HIP(hipGetLastError());
     *increment = inc * 4ull;
+    return VMAS_OK;
+}
+
+extern "C" int32_t vmas_spawn_reset(int32_t device, const VmasSpawnResetIO* io, uint64_t* increment, int32_t* unresolved,
+                                    void* stream) {
+    if (!io || !increment || !unresolved || device < 0 || device >= 64)
+        return vmas_aux::fail(VMAS_E_INVALID, "vmas_spawn_reset: bad arguments");
+    if (io->batch <= 0 || io->n_place < 1 || io->n_place > VMAS_RESET_MAX_PLACE || io->n_fixed < 0 ||
+        io->n_fixed > VMAS_RESET_MAX_FIXED || io->n_write < 0 || io->n_write > VMAS_RESET_MAX_WRITE || io->n_agents < 0 ||
+        io->n_agents > VMAS_RESET_MAX_AGENTS || io->n_derived < 0 || io->n_derived > VMAS_RESET_MAX_DERIVED || !io->mask ||
+        !io->scratch || !io->words || io->mode < 0 || io->mode > 3)
+        return vmas_aux::fail(VMAS_E_INVALID, "vmas_spawn_reset: bad arguments (batch %d, %d placed, %d written)",
+                              io->batch, io->n_place, io->n_write);
+    for (int j = 0; j < io->n_fixed; ++j)
+        if (!io->fixed[j].p) return vmas_aux::fail(VMAS_E_INVALID, "vmas_spawn_reset: null fixed position %d", j);
+    for (int w = 0; w < io->n_write; ++w)
+        if (io->write_slot[w] < 0 || io->write_slot[w] >= io->n_place)
+            return vmas_aux::fail(VMAS_E_INVALID, "vmas_spawn_reset: entity %d reads slot %d of %d", w, io->write_slot[w],
+                                  io->n_place);
+    for (int d = 0; d < io->n_derived; ++d) {
+        const VmasResetDerived& r = io->derived[d];
+        const bool slots = r.a >= 0 && r.a < io->n_place && r.b >= 0 && r.b < io->n_place;
+        const bool ok = r.kind == VMAS_RESET_D_NORM         ? slots && r.out.p
+                        : r.kind == VMAS_RESET_D_BOX_SPHERE ? slots && r.out8
+                        : r.kind == VMAS_RESET_D_CLEAR8     ? r.out8 && r.n >= 0
+                                                            : false;
+        if (!ok) return vmas_aux::fail(VMAS_E_INVALID, "vmas_spawn_reset: derived value %d (kind %d)", d, r.kind);
+    }
+    std::lock_guard<std::mutex> lk(g_reset_mu);
+    VMAS_AUX_HIP(hipSetDevice(device));
+    static int max_blocks[64] = {0};
+    if (!max_blocks[device]) {
+        hipDeviceProp_t prop;
+        VMAS_AUX_HIP(hipGetDeviceProperties(&prop, device));
+        max_blocks[device] = prop.multiProcessorCount * (prop.maxThreadsPerMultiProcessor / vmas_uniform::kThreads);
+        if (max_blocks[device] <= 0) return vmas_aux::fail(VMAS_E_HIP, "vmas_spawn_reset: device properties");
+    }
+    if (!g_reset_host_words[device])
+        VMAS_AUX_HIP(hipHostMalloc((void**)&g_reset_host_words[device], VMAS_RESET_WORDS * sizeof(int32_t),
+                                   hipHostMallocDefault));
+    int32_t* h = g_reset_host_words[device];
+    // torch's distribution-kernel grid and per-call philox increment on B elements
+    int gx_draw = 0;
+    unsigned long long inc = 0;
+    vmas_uniform::grid_for(io->batch, max_blocks[device], &gx_draw, &inc);
+    const vmas_uniform::DrawGrid g{(long long)vmas_uniform::kThreads * gx_draw, inc};
+    hipStream_t st = (hipStream_t)stream;
+    const int gx = (io->batch + kResetThreads - 1) / kResetThreads;
+    // (the words are zeroed by a kernel, not a memset: vmas_spawn.hip k_spawn_clear has the note)
+    VMAS_AUX_HIP(vmas_aux::fill_u32_async(io->words, 0u, VMAS_RESET_WORDS, st));
+    PlaceArgs a{};
+    a.batch = io->batch;
+    a.n_fixed = io->n_fixed;
+    a.max_tries = io->max_tries > 0 ? std::min(io->max_tries, VMAS_RESET_TRIES_LIMIT) : VMAS_RESET_TRIES_LIMIT;
+    a.mode = io->mode;
+    a.x_lo = io->x_lo, a.x_hi = io->x_hi, a.y_lo = io->y_lo, a.y_hi = io->y_hi;
+    a.seed = io->seed, a.offset = io->offset;
+    a.scratch = io->scratch, a.words = io->words;
+    for (int j = 0; j < io->n_fixed; ++j) a.fixed[j] = io->fixed[j];
+    for (int i = 0; i < io->n_place; ++i) {
+        a.index = i;
+        a.d2_min = vmas_aux::spawn_d2_min(io->min_dist[i]);
+        hipLaunchKernelGGL(k_reset_place, dim3(gx), dim3(kResetThreads), 0, st, a, g);
+    }
+    hipLaunchKernelGGL(k_reset_commit, dim3(gx), dim3(kResetThreads), 0, st, *io);
+    VMAS_AUX_HIP(hipGetLastError());
+    VMAS_AUX_HIP(hipMemcpyAsync(h, io->words, VMAS_RESET_WORDS * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    vmas_aux::note_host_wait();
+    VMAS_AUX_HIP(hipStreamSynchronize(st));  // the call's only wait
+    unsigned long long tries = 0;
+    for (int i = 0; i < io->n_place; ++i) tries += (unsigned long long)(h[i] == 0 ? 1 : h[i] + 2);
+    *increment = tries * 2ull * inc;
+    *unresolved = h[VMAS_RESET_MAX_PLACE];
     return VMAS_OK;
 }

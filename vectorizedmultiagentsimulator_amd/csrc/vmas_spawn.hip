@@ -1133,22 +1133,8 @@ size_t win_chain_lds_bytes(int T) {
     return cap * (44 * T + 8) + (size_t)T * kWinMaxPairs;
 }
 
-// The smallest float x >= 0 with sqrtf(x) >= min_dist (binary search over the ordered bit patterns
-// of non-negative floats; sqrtf is correctly rounded on the host as on the device).
-float spawn_d2_min(float min_dist) {
-    if (!(min_dist > 0.f)) return 0.f;  // sqrt(d2) < min_dist never holds: neither does d2 < 0
-    uint32_t lo = 0u, hi = 0x7f800000u;  // sqrtf(+inf) = inf >= min_dist
-    while (lo < hi) {
-        const uint32_t mid = lo + (hi - lo) / 2u;
-        float x;
-        memcpy(&x, &mid, 4);
-        if (sqrtf(x) >= min_dist) hi = mid;
-        else lo = mid + 1u;
-    }
-    float r;
-    memcpy(&r, &lo, 4);
-    return r;
-}
+// (the smallest float whose sqrtf reaches min_dist: vmas_aux.hpp, shared with vmas_reset.hip)
+using vmas_aux::spawn_d2_min;
 
 }  // namespace
 

@@ -106,6 +106,37 @@ class Scenario(BaseScenario):
         for target in self._targets[self.n_targets:]:
             target.set_pos(self.get_outside_pos(env_index), batch_index=env_index)
 
+    # ---- masked reset (Environment.reset_where; csrc/vmas_reset.hip vmas_spawn_reset) -----------
+    # The rows of `mask` as reset_world_at(None) after World.reset leaves them, in place: the
+    # targets and then the agents placed by the reference's loop on the device,
+    # all_time_covered_targets cleared.  (Target landmarks beyond n_targets would take further
+    # draws, get_outside_pos: the generic path then.)
+    native_resets = 0           # calls the launch chain answered (a test's proof that no fall-back ran)
+    native_reset_fallbacks = 0  # calls handed to the generic path because an env passed spawn_max_tries
+
+    @property
+    def spawn_max_tries(self) -> int:
+        """Tries per entity before a call goes to the generic path (0: the kernel's limit); the
+        respawn's spawn_max_tries() unless set."""
+        v = self.__dict__.get("_spawn_max_tries")
+        return spawn_max_tries() if v is None else v
+
+    @spawn_max_tries.setter
+    def spawn_max_tries(self, value: int):
+        self._spawn_max_tries = int(value)
+
+    def reset_world_where(self, mask):
+        from vectorizedmultiagentsimulator_amd.simulator.environment._spawn_reset import spawn_reset_where
+
+        w = self.world
+        if self.n_targets < 1 or len(self._targets) > self.n_targets or getattr(self, "all_time_covered_targets", None) is None:
+            return NotImplemented
+        placable = self._targets[: self.n_targets] + w.agents
+        return spawn_reset_where(
+            self, mask, [([e.name for e in placable], self._min_dist_between_entities)],
+            [(e, e.name) for e in placable], (-w.x_semidim, w.x_semidim), (-w.y_semidim, w.y_semidim),
+            derived=[("clear", self.all_time_covered_targets)], max_tries=self.spawn_max_tries)
+
     def reward(self, agent: Agent):
         if _fused.enabled(self.world) and self._fused_plan() is not None:
             return self._fused_reward(agent)

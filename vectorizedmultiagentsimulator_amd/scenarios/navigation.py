@@ -154,6 +154,35 @@ class Scenario(BaseScenario):
                     * self.pos_shaping_factor
                 )
 
+    # ---- masked reset (Environment.reset_where; csrc/vmas_reset.hip vmas_spawn_reset) -----------
+    # The rows of `mask` as reset_world_at(None) after World.reset leaves them, in place: the agents
+    # and then one goal position per agent placed by the reference's loop on the device, every
+    # agent's goal at the position its goal index names, pos_shaping from the new positions.
+    native_resets = 0           # calls the launch chain answered (a test's proof that no fall-back ran)
+    native_reset_fallbacks = 0  # calls handed to the generic path because an env passed spawn_max_tries
+    spawn_max_tries = 0         # tries per entity before that happens (0: the kernel's limit)
+
+    def reset_world_where(self, mask):
+        from vectorizedmultiagentsimulator_amd.simulator.environment._spawn_reset import spawn_reset_where
+
+        agents = self.world.agents
+        if any(not isinstance(getattr(a, "pos_shaping", None), Tensor) for a in agents):
+            return NotImplemented
+        writes, derived = [], []
+        for i, a in enumerate(agents):
+            if self.split_goals:
+                goal_index = int(i // self.agents_with_same_goal)
+            else:
+                goal_index = 0 if i < self.agents_with_same_goal else i
+            writes += [(a, ("agent", i)), (a.goal, ("goal", goal_index))]
+            derived.append(("norm", ("agent", i), ("goal", goal_index), self.pos_shaping_factor, a.pos_shaping))
+        n = len(agents)
+        keys = [("agent", i) for i in range(n)] + [("goal", i) for i in range(n)]
+        return spawn_reset_where(
+            self, mask, [(keys, self.min_distance_between_entities)], writes,
+            (-self.world_spawning_x, self.world_spawning_x), (-self.world_spawning_y, self.world_spawning_y),
+            derived=derived, max_tries=self.spawn_max_tries)
+
     def reward(self, agent: Agent):
         if _fused.enabled(self.world) and self._fused_plan() is not None:
             return self._fused_reward(agent)

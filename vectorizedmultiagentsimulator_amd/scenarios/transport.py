@@ -80,6 +80,37 @@ class Scenario(BaseScenario):
             else:
                 package.global_shaping[env_index] = dist[env_index] * self.shaping_factor
 
+    # ---- masked reset (Environment.reset_where; csrc/vmas_reset.hip vmas_spawn_reset) -----------
+    # The rows of `mask` as reset_world_at(None) after World.reset leaves them, in place: the two
+    # spawn calls above as one chain of placements on the device (the agents at their distance, the
+    # goal and the packages at theirs from everything before), then every package's on_goal and
+    # global_shaping from the new positions.
+    native_resets = 0           # calls the launch chain answered (a test's proof that no fall-back ran)
+    native_reset_fallbacks = 0  # calls handed to the generic path because an env passed spawn_max_tries
+    spawn_max_tries = 0         # tries per entity before that happens (0: the kernel's limit)
+
+    def reset_world_where(self, mask):
+        from vectorizedmultiagentsimulator_amd.simulator.environment._spawn_reset import spawn_reset_where
+
+        w = self.world
+        goal = w.landmarks[0]
+        if not self._fused_ok() or any(getattr(p, "on_goal", None) is None or getattr(p, "global_shaping", None) is None
+                                       for p in self.packages):
+            return NotImplemented
+        second = [goal] + self.packages
+        stages = [
+            ([e.name for e in w.agents], self.agent_radius * 2),
+            ([e.name for e in second], max(p.shape.circumscribed_radius() + goal.shape.radius + 0.01
+                                           for p in self.packages)),
+        ]
+        derived = []
+        for p in self.packages:
+            derived.append(("box_sphere", p, p.goal, p.name, p.goal.name, p.on_goal))
+            derived.append(("norm", p.name, p.goal.name, self.shaping_factor, p.global_shaping))
+        bounds = (-self.world_semidim, self.world_semidim)
+        return spawn_reset_where(self, mask, stages, [(e, e.name) for e in list(w.agents) + second], bounds, bounds,
+                                 derived=derived, max_tries=self.spawn_max_tries)
+
     def reward(self, agent: Agent):
         if _fused.enabled(self.world) and self._fused_ok():
             return self._fused_reward(agent)
