@@ -12,6 +12,7 @@
 #include <hip/hip_runtime.h>
 
 #include "vmas_aux.hpp"
+#include "vmas_lidar.hpp"
 #include "vmas_mi355x.h"
 #include "vmas_programs.hpp"
 #include "vmas_query.hpp"
@@ -19,12 +20,6 @@
 using namespace vmas;
 
 namespace {
-
-// __sinf / __cosf (v_sin_f32 / v_cos_f32) take the angle in revolutions: x * (1 / 2 pi) rounds to
-// |x| * 2^-24 rad, i.e. 1e-6 rad at 16 rad (the LIDAR certification's turn, tests/_parity.py) and
-// 1.5e-5 rad at 256.  Below this bound the fast LIDAR programs use them; above it ocml's
-// range-reduced sincosf.  (Ray angles are the sensor's [0, 2 pi) plus the agent's rotation.)
-constexpr float kFastTrigMaxAngle = 16.f;
 
 // balance.py:205-262 (restated in scenarios/balance.py): reward of the first agent (on-the-ground
 // test, package-goal distance, ground / position rewards and the global shaping update), every
@@ -80,7 +75,7 @@ struct FlockHead {
     float v[6];
 };
 // IO: the argument block by value, or (k_flocking_fast) read in place through the kernel
-// argument segment pointer -- structs copied out before use, see k_flocking_fast.
+// argument segment (VMAS_PROGRAM_ARGS) -- structs copied out before use.
 template <class IO>
 __device__ __forceinline__ FlockHead flock_part0(IO& io, int b, int p, const OutDelta& od, bool ret = false) {
     FlockHead h{};
@@ -198,42 +193,23 @@ __global__ void __launch_bounds__(64) k_flocking(VmasFlockingIO io) {
     moved(io.obs[p], od.obs)[(long)b * W + 6 + r] = best;
 }
 
-// The same program with the fast LIDAR (io.fast_lidar, the default): the ray-sphere distance in
-// its direct form (ray_sphere_fast), hardware sin / cos / sqrt.  Grid: x = 64-env groups, y =
-// groups of 4 policy agents; a wave per (64 envs, agent): its reward / head (flock_part0) and all
-// of its rays (angles and targets loaded up front), the observation rows staged in LDS and
-// written out as contiguous blocks (a lane per env writes 4-byte values 4 * W bytes apart
-// otherwise: twice the output bytes reached HBM).  History (32 768 envs x 8 agents): a thread per
-// ray of the exact program, 53 us; a thread per (env, agent) with ocml sincosf and per-ray angle
-// loads, 89 us; waves over ray subsets with wave 0 also doing the reward, 48 us.
+// The same program with the fast LIDAR (io.fast_lidar, the default; RayHardware).  Grid: x = 64-env
+// groups, y = groups of 4 policy agents; a wave per (64 envs, agent): its reward / head
+// (flock_part0) and all of its rays (angles and targets loaded up front), the observation rows
+// staged in LDS.  NR / NT > 0: the ray and target counts fixed at compile time (flocking's 12 rays;
+// instantiated for 1..8 targets), the unrolled form of lidar_row with the LIDAR row split by a
+// constant; otherwise its runtime form.  History (32 768 envs x 8 agents): a thread per ray of the
+// exact program, 53 us; a thread per (env, agent) with ocml sincosf and per-ray angle loads, 89 us;
+// waves over ray subsets with wave 0 also doing the reward, 48 us.
 constexpr int kFlockFastRays = 16, kFlockFastTargets = 8, kFlockFastW = 6 + kFlockFastRays;
-#ifdef __HIP_DEVICE_COMPILE__
-typedef const VmasFlockingIO __attribute__((address_space(4))) KFlockingIO;  // (the device pass)
-#else
-typedef const VmasFlockingIO KFlockingIO;  // (the host pass only parses the kernel)
-#endif
-// NR / NT > 0: the ray and target counts fixed at compile time (flocking's 12 rays; instantiated
-// for 1..8 targets): every ray unrolled with its angle in a register, so the rays' chains
-// interleave (the rolled loop left each wave one ray's dependent chain at a time, at 4 waves per
-// SIMD), no per-target branch, and the LIDAR row split by a constant.  Same operations per ray
-// in the same order as the runtime form (bit-identical).
 template <int NR, int NT>
 __global__ void __launch_bounds__(256) k_flocking_fast(VmasFlockingIO io_arg) {
     constexpr int RM = NR > 0 ? NR : kFlockFastRays, TM = NT > 0 ? NT : kFlockFastTargets;
-    // The argument block read in place (s_load from the kernel argument segment): indexed by the
-    // wave's agent, the by-value parameter was copied to scratch (3.5 KiB per lane)
-#ifdef __HIP_DEVICE_COMPILE__
-    KFlockingIO& io = *(KFlockingIO*)__builtin_amdgcn_kernarg_segment_ptr();
-    (void)io_arg;
-#else
-    KFlockingIO& io = io_arg;
-#endif
+    VMAS_PROGRAM_ARGS(VmasFlockingIO, io_arg);
     __shared__ float S[4][64 * kFlockFastW];
     const int lane = (int)(threadIdx.x & 63u), w = (int)(threadIdx.x >> 6);
-    // (p made wave-uniform for the compiler: indexing the argument block's arrays with a per-lane
-    // index copies the whole 3.5 KiB block to scratch)
     const int g0 = (int)blockIdx.x * 64, b = g0 + lane;
-    const int p = __builtin_amdgcn_readfirstlane((int)blockIdx.y * 4 + w);
+    const int p = wave_uniform((int)blockIdx.y * 4 + w);
     if (p >= io.n_policy) return;  // (wave-uniform; no workgroup barrier below)
     const bool valid = b < io.batch;
     const int nr = NR > 0 ? NR : io.n_rays, nt = NT > 0 ? NT : io.n_ray_targets, W = 6 + nr;
@@ -266,64 +242,15 @@ __global__ void __launch_bounds__(256) k_flocking_fast(VmasFlockingIO io_arg) {
 #pragma unroll
             for (int i = 0; i < 6; ++i) S[w][row + i] = h.v[i];
         }
-        // (loops fully unrolled with guarded bodies, never `break`: a partly unrolled loop indexes
-        // A / T dynamically, which puts them in scratch)
         float C[TM];
 #pragma unroll
-        for (int t = 0; t < TM; ++t) C[t] = R2[t] - (T[t].x * T[t].x + T[t].y * T[t].y);
-        if constexpr (NR > 0 && NT > 0) {
-#pragma unroll
-            for (int r = 0; r < NR; ++r) {
-                const float a = A[r] + rot;
-                // hardware sin / cos (v_sin / v_cos_f32) below kFastTrigMaxAngle, ocml's
-                // range-reduced sincosf above (see kFastTrigMaxAngle)
-                float ds, dc;
-                if (fabsf(a) < kFastTrigMaxAngle) {
-                    ds = __sinf(a);
-                    dc = __cosf(a);
-                } else {
-                    sincosf(a, &ds, &dc);
-                }
-                float best = io.max_range;
-#pragma unroll
-                for (int t = 0; t < NT; ++t) best = min_drop_nan(best, ray_sphere_fast_nan(T[t].x, T[t].y, C[t], dc, ds));
-                S[w][row + 6 + r] = best;
-            }
-        } else {
-            // rays in a rolled loop, targets unrolled inside (see k_discovery_obs_fast)
-            // (the angles wait in the rays' own LDS slots: a register array indexed at run time
-            // goes to scratch)
-#pragma unroll
-            for (int r = 0; r < RM; ++r)
-                if (r < nr) S[w][row + 6 + r] = A[r] + rot;
-#pragma unroll 1
-            for (int r = 0; r < nr; ++r) {
-                const float a = S[w][row + 6 + r];
-                float ds, dc;
-                if (fabsf(a) < kFastTrigMaxAngle) {
-                    ds = __sinf(a);
-                    dc = __cosf(a);
-                } else {
-                    sincosf(a, &ds, &dc);
-                }
-                float best = io.max_range;
-#pragma unroll
-                for (int t = 0; t < TM; ++t) {
-                    if (t >= nt) continue;
-                    best = min_drop_nan(best, ray_sphere_fast_nan(T[t].x, T[t].y, C[t], dc, ds));
-                }
-                S[w][row + 6 + r] = best;
-            }
-        }
-        // the wave's rows out as contiguous blocks: obs [64 x W], the LIDAR [64 x nr]
+        for (int t = 0; t < TM; ++t) C[t] = RayHardware::c(R2[t], T[t]);
+        lidar_row<RayHardware, (NR > 0 && NT > 0), RM, 1>(
+            S[w] + row + 6, nr, [&](int r) { return A[r] + rot; }, T, C, io.max_range,
+            [&](int t) { return NT > 0 || t < nt; });
         const int nv = io.batch - g0 < 64 ? io.batch - g0 : 64;
-        float* obs = moved(io.obs[p], od.obs) + (long)g0 * W;
-        for (int i = lane; i < nv * W; i += 64) obs[i] = S[w][i];
-        float* lid = io.lidar[p] + (long)g0 * nr;
-        for (int i = lane; i < nv * nr; i += 64) {
-            const int e = i / nr;
-            lid[i] = S[w][e * W + 6 + (i - e * nr)];
-        }
+        rows_out(S[w], nv, W, moved(io.obs[p], od.obs) + (long)g0 * W, lane, 64, nullptr,
+                 io.lidar[p] + (long)g0 * nr, 6, nr, lane);
     } else if (valid) {
         flock_part0(io, b, p, od);
     }
@@ -529,30 +456,19 @@ __device__ __forceinline__ void nav_head(IO& io, int bb, int k, const V2* P, con
     }
 }
 
-#ifdef __HIP_DEVICE_COMPILE__
-typedef const VmasNavigationIO __attribute__((address_space(4))) KNavigationIO;  // (see k_flocking_fast)
-#else
-typedef const VmasNavigationIO KNavigationIO;
-#endif
-
 // The program with the LIDAR bit-identical to k_cast_rays (io.fast_lidar == 0, or a shape over the
 // fast form's caps).  Grid as k_flocking: x = 64-env groups, y = (agent k, part): part 0 is k's
 // reward, done (k == 0) and the observation head, part 1 + r is ray r of k's LIDAR over the other
 // agents in order.
 __global__ void __launch_bounds__(64) k_navigation(VmasNavigationIO io_arg) {
     constexpr int MA = kNavMA;
-#ifdef __HIP_DEVICE_COMPILE__
-    KNavigationIO& io = *(KNavigationIO*)__builtin_amdgcn_kernarg_segment_ptr();
-    (void)io_arg;
-#else
-    KNavigationIO& io = io_arg;
-#endif
+    VMAS_PROGRAM_ARGS(VmasNavigationIO, io_arg);
     const int lane = (int)threadIdx.x, b = (int)blockIdx.x * 64 + lane;
     const bool valid = b < io.batch;
     const int bb = valid ? b : io.batch - 1;
     const int nr = io.lidar_on ? io.n_rays : 0;
     const int parts = (io.what & VMAS_SCN_OBS) ? 1 + nr : 1;
-    const int k = __builtin_amdgcn_readfirstlane((int)blockIdx.y / parts);
+    const int k = wave_uniform((int)blockIdx.y / parts);
     const int part = (int)blockIdx.y - k * parts;
     const int H = 4 + 2 * (io.observe_all_goals ? io.n_agents : 1), W = H + nr;
     const OutDelta od = load_out_delta(io);
@@ -580,76 +496,27 @@ __global__ void __launch_bounds__(64) k_navigation(VmasNavigationIO io_arg) {
 }
 
 __global__ void __launch_bounds__(1024) k_navigation_pairs(VmasNavigationIO io_arg) {
-#ifdef __HIP_DEVICE_COMPILE__
-    KNavigationIO& io = *(KNavigationIO*)__builtin_amdgcn_kernarg_segment_ptr();
-    (void)io_arg;
-#else
-    KNavigationIO& io = io_arg;
-#endif
+    VMAS_PROGRAM_ARGS(VmasNavigationIO, io_arg);
     __shared__ uint32_t EN[kNavMA];
     nav_pairs(io, load_out_delta(io), (int)threadIdx.x, (int)blockDim.x, EN);
 }
 
-// The fast LIDAR's ray direction and ray-sphere distance.  k_flocking_fast's pair (hardware sin /
-// cos, ray_sphere_fast_nan) was measured first and missed the LIDAR parity condition here: at
-// navigation's geometry (centres up to 0.45 from the origin, radius 0.1, positions of magnitude 1)
-// the direct form's r^2 - dn^2 = t^2 + (r^2 - |u|^2) cancels to ~5e-8 in `a`, and the hardware
-// instructions turn the ray by up to ~3e-7 rad (another ~3e-8 in `a`); a grazing hit (a ~ 1e-7)
-// then lands 6.7e-5 from the oracle, beyond what a certification turn reproduces (2 of 16 384 rows
-// at 4 096 envs).  So: dn as the cross product u x dir (no cancellation: ~6e-9 in `a`), and the
-// direction from a Cody-Waite reduction by pi / 2 with the Cephes sinf / cosf polynomials (angle
-// error <= 1e-7 rad against double precision over +-16 rad, ~20 VALU a ray), ocml's sincosf beyond
-// kFastTrigMaxAngle.  NaN on a miss, dropped by min_drop_nan, as ray_sphere_fast_nan.
-__device__ __forceinline__ void nav_sincos(float x, float& s, float& c) {
-    if (!(fabsf(x) < kFastTrigMaxAngle)) {
-        sincosf(x, &s, &c);
-        return;
-    }
-    const float k = rintf(x * 0.636619772f);  // 2 / pi
-    float r = __builtin_fmaf(-k, 1.5703125f, x);  // pi / 2 in three parts; the first product is exact
-    r = __builtin_fmaf(-k, 4.837512969970703125e-4f, r);
-    r = __builtin_fmaf(-k, 7.54978995489188216e-8f, r);
-    const float z = r * r;
-    float ps = __builtin_fmaf(-1.9515295891e-4f, z, 8.3321608736e-3f);
-    ps = __builtin_fmaf(ps, z, -1.6666654611e-1f);
-    const float sr = __builtin_fmaf(r * z, ps, r);
-    float pc = __builtin_fmaf(2.443315711809948e-5f, z, -1.388731625493765e-3f);
-    pc = __builtin_fmaf(pc, z, 4.166664568298827e-2f);
-    const float cr = __builtin_fmaf(z * z, pc, __builtin_fmaf(-0.5f, z, 1.0f));
-    const int q = (int)k & 3;
-    const float a = (q & 1) ? cr : sr, b = (q & 1) ? sr : cr;
-    s = (q & 2) ? -a : a;
-    c = ((q + 1) & 2) ? -b : b;
-}
-__device__ __forceinline__ float nav_ray_nan(float ux, float uy, float r2, float dc, float ds) {
-    const float t = __builtin_fmaf(ux, dc, uy * ds);      // the foot point's distance along the ray
-    const float dn = __builtin_fmaf(ux, ds, -(uy * dc));  // the centre's distance from the ray's line
-    const float a = __builtin_fmaf(-dn, dn, r2);
-    return t - __builtin_amdgcn_sqrtf(__builtin_fminf(a, t * 1e30f));
-}
-
-// The same program with the fast LIDAR (io.fast_lidar, the default), laid out as k_flocking_fast:
-// grid x = 64-env groups, y = groups of 4 agents; a wave per (64 envs, agent): its reward, its
-// observation head and all of its rays (angles, positions and goals loaded up front; nav_sincos /
-// nav_ray_nan above), the rows staged in LDS (4 x 64 x W floats, sized by the launch) and written
-// out as contiguous blocks.  NR / NT > 0: the ray and target counts fixed at compile time (12
-// rays; 1..7 targets, i.e. 2..8 agents), every ray unrolled; otherwise the rolled runtime form.
-// The LIDAR's targets are the other agents in order.
+// The same program with the fast LIDAR (io.fast_lidar, the default; RayPrecise), laid out as
+// k_flocking_fast: grid x = 64-env groups, y = groups of 4 agents; a wave per (64 envs, agent): its
+// reward, its observation head and all of its rays (angles, positions and goals loaded up front),
+// the rows staged in LDS (4 x 64 x W floats, sized by the launch).  NR / NT > 0: the ray and target
+// counts fixed at compile time (12 rays; 1..7 targets, i.e. 2..8 agents), the unrolled form of
+// lidar_row; otherwise its runtime form.  The LIDAR's targets are the other agents in order.
 constexpr int kNavFastRays = 16, kNavFastTargets = kNavMA - 1;
 template <int NR, int NT>
 __global__ void __launch_bounds__(256) k_navigation_fast(VmasNavigationIO io_arg) {
     constexpr int RM = NR > 0 ? NR : kNavFastRays, TM = NT > 0 ? NT : kNavFastTargets;
     constexpr int NA = NT > 0 ? NT + 1 : kNavMA;
-#ifdef __HIP_DEVICE_COMPILE__
-    KNavigationIO& io = *(KNavigationIO*)__builtin_amdgcn_kernarg_segment_ptr();
-    (void)io_arg;
-#else
-    KNavigationIO& io = io_arg;
-#endif
+    VMAS_PROGRAM_ARGS(VmasNavigationIO, io_arg);
     extern __shared__ float nav_lds[];
     const int lane = (int)(threadIdx.x & 63u), w = (int)(threadIdx.x >> 6);
     const int g0 = (int)blockIdx.x * 64, b = g0 + lane;
-    const int k = __builtin_amdgcn_readfirstlane((int)blockIdx.y * 4 + w);
+    const int k = wave_uniform((int)blockIdx.y * 4 + w);
     const int n = io.n_agents;
     if (k >= n) return;  // (wave-uniform; no workgroup barrier below)
     const bool valid = b < io.batch;
@@ -687,58 +554,17 @@ __global__ void __launch_bounds__(256) k_navigation_fast(VmasNavigationIO io_arg
         const V2 pt = t + 1 < NA ? (t < k ? P[t] : P[t + 1]) : P[t];
         const float rad = io.agents[t < k ? t : t + 1].radius;
         T[t] = t < nt ? pt - pk : mk(0.f, 0.f);
-        C[t] = rad * rad;  // (r^2)
+        C[t] = RayPrecise::c(rad * rad, T[t]);
     }
     nav_head<NA>(io, bb, k, P, G, S + row);
     if (io.what & VMAS_SCN_REWARD) nav_reward<NA>(io, b, valid, k, lane, od, P, G);
     else if ((io.what & VMAS_SCN_DONE) && k == 0 && valid) moved(io.done, od.done)[b] = nav_done<NA>(io, P, G) ? 1 : 0;
-    // (loops fully unrolled with guarded bodies, never `break`: see k_flocking_fast)
-    if constexpr (NR > 0 && NT > 0) {
-#pragma unroll
-        for (int r = 0; r < NR; ++r) {
-            const float a = A[r] + rot;
-            float ds, dc;
-            nav_sincos(a, ds, dc);
-            float best = io.max_range;
-#pragma unroll
-            for (int t = 0; t < NT; ++t) best = min_drop_nan(best, nav_ray_nan(T[t].x, T[t].y, C[t], dc, ds));
-            S[row + H + r] = best;
-        }
-    } else {
-        // rays in a rolled loop, targets unrolled inside; the angles wait in the rays' own LDS slots
-#pragma unroll
-        for (int r = 0; r < RM; ++r)
-            if (r < nr) S[row + H + r] = A[r] + rot;
-#pragma unroll 1
-        for (int r = 0; r < nr; ++r) {
-            const float a = S[row + H + r];
-            float ds, dc;
-            nav_sincos(a, ds, dc);
-            float best = io.max_range;
-#pragma unroll
-            for (int t = 0; t < TM; ++t) {
-                if (t >= nt) continue;
-                best = min_drop_nan(best, nav_ray_nan(T[t].x, T[t].y, C[t], dc, ds));
-            }
-            S[row + H + r] = best;
-        }
-    }
-    // the wave's rows out as contiguous blocks: obs [64 x W] (its LIDAR columns max_range - the
-    // measurement), the measurements [64 x nr]
+    lidar_row<RayPrecise, (NR > 0 && NT > 0), RM, 1>(
+        S + row + H, nr, [&](int r) { return A[r] + rot; }, T, C, io.max_range, [&](int t) { return NT > 0 || t < nt; });
+    // (the observation's LIDAR columns are max_range - the measurement)
     const int nv = io.batch - g0 < 64 ? io.batch - g0 : 64;
-    float* obs = moved(io.obs[k], od.obs) + (long)g0 * W;
-    for (int i = lane; i < nv * W; i += 64) {
-        const int c = i - (i / W) * W;
-        const float v = S[i];
-        obs[i] = c >= H ? io.max_range - v : v;
-    }
-    if (nr > 0) {
-        float* lid = io.lidar[k] + (long)g0 * nr;
-        for (int i = lane; i < nv * nr; i += 64) {
-            const int e = i / nr;
-            lid[i] = S[e * W + H + (i - e * nr)];
-        }
-    }
+    rows_out(S, nv, W, moved(io.obs[k], od.obs) + (long)g0 * W, lane, 64,
+             [&](int c, float v) { return c >= H ? io.max_range - v : v; }, io.lidar[k] + (long)g0 * nr, H, nr, lane);
 }
 
 // flocking's scripted target: u = stack([cos(t / period), sin(t / period)], dim=1) (the division
@@ -900,14 +726,6 @@ __global__ void __launch_bounds__(64) k_discovery_obs(VmasDiscoveryIO io) {
     o[col + r] = best;
 }
 
-#ifdef __HIP_DEVICE_COMPILE__
-typedef const VmasDiscoveryIO __attribute__((address_space(4))) KDiscoveryIO;  // (see k_flocking_fast)
-#define VMAS_KARG(T, name) T& io = *(T*)__builtin_amdgcn_kernarg_segment_ptr(); (void)name
-#else
-typedef const VmasDiscoveryIO KDiscoveryIO;
-#define VMAS_KARG(T, name) T& io = name
-#endif
-
 // REWARD with a wave per agent (k_discovery_reward has one thread per env: 256 waves for 16 384
 // envs, 31.5 us): lane = env of the workgroup's 64, wave i = agent i.  The agents' in-range bits
 // meet in LDS for the per-target counts; wave 0 sums the covering rewards in agent order (the
@@ -915,7 +733,7 @@ typedef const VmasDiscoveryIO KDiscoveryIO;
 // LDS and written out as contiguous blocks.
 constexpr int kDiscFastAgents = 16, kDiscFastTargets = 16;
 __global__ void __launch_bounds__(1024) k_discovery_reward_fast(VmasDiscoveryIO io_arg) {
-    VMAS_KARG(KDiscoveryIO, io_arg);
+    VMAS_PROGRAM_ARGS(VmasDiscoveryIO, io_arg);
     disc_stage(io);
     constexpr int MT = kDiscFastTargets;
     __shared__ float D[64 * kDiscFastAgents * kDiscFastTargets];  // dists rows of the 64 envs (64 KiB)
@@ -923,7 +741,7 @@ __global__ void __launch_bounds__(1024) k_discovery_reward_fast(VmasDiscoveryIO 
     __shared__ float CR[kDiscFastAgents][64];                     // agent i's covering reward
     __shared__ float SH[64];
     const int lane = (int)(threadIdx.x & 63u);
-    const int i = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int i = wave_uniform((int)(threadIdx.x >> 6));
     const int A = io.n_agents, T = io.n_targets, g0 = (int)blockIdx.x * 64, b = g0 + lane;
     const bool valid = b < io.batch;
     const int bb = valid ? b : io.batch - 1;
@@ -1010,11 +828,11 @@ __global__ void __launch_bounds__(1024) k_discovery_reward_fast(VmasDiscoveryIO 
 constexpr int kDiscFastEntities = 16, kDiscFastRays = 16;  // per LIDAR
 constexpr int kDiscFastW = 4 + VMAS_DISC_MAX_LIDARS * kDiscFastRays;
 __global__ void __launch_bounds__(256) k_discovery_obs_fast(VmasDiscoveryIO io_arg) {
-    VMAS_KARG(KDiscoveryIO, io_arg);
+    VMAS_PROGRAM_ARGS(VmasDiscoveryIO, io_arg);
     constexpr int ME = kDiscFastEntities, RM = kDiscFastRays;
     __shared__ float S[4][64 * kDiscFastW];
     const int lane = (int)(threadIdx.x & 63u), w = (int)(threadIdx.x >> 6);
-    const int a = __builtin_amdgcn_readfirstlane((int)blockIdx.y * 4 + w);
+    const int a = wave_uniform((int)blockIdx.y * 4 + w);
     if (a >= io.n_agents) return;  // (wave-uniform; no workgroup barrier below)
     const int g0 = (int)blockIdx.x * 64, b = g0 + lane;
     const bool valid = b < io.batch;
@@ -1047,62 +865,15 @@ __global__ void __launch_bounds__(256) k_discovery_obs_fast(VmasDiscoveryIO io_a
     for (int s = 0; s < io.n_lidars; ++s) {
         const uint32_t mask = io.mask[s] & ~(1u << self);  // World.cast_rays skips the entity itself
         const int nr = io.n_rays[s];
-        const float mr = io.max_range[s];
         const float* ang = io.angles[s][a] + (long)bb * io.ang_s0[s][a];
         const int as1 = io.ang_s1[s][a];
-        // rays in a rolled loop (entities unrolled inside, a uniform branch on the LIDAR's mask):
-        // the fully unrolled rays x entities body was ~35 KiB of straight-line code, each wave
-        // streaming it through the instruction cache once
-        // (the angles, loaded together up front, wait in the rays' own LDS slots)
-        // (rays in pairs: two rays' independent chains interleave -- at 4 waves per SIMD one chain
-        // at a time left the SIMDs waiting; the same operations per ray, in the same order)
-#pragma unroll
-        for (int r = 0; r < RM; ++r)
-            if (r < nr) S[w][row + col + r] = ang[(long)r * as1] + rot;
-        auto sc = [](float th, float& ds, float& dc) {
-            if (fabsf(th) < kFastTrigMaxAngle) {
-                ds = __sinf(th);
-                dc = __cosf(th);
-            } else {
-                sincosf(th, &ds, &dc);
-            }
-        };
-        int r = 0;
-#pragma unroll 1
-        for (; r + 1 < nr; r += 2) {
-            float dc0, ds0, dc1, ds1;
-            sc(S[w][row + col + r], ds0, dc0);
-            sc(S[w][row + col + r + 1], ds1, dc1);
-            float b0 = mr, b1 = mr;
-#pragma unroll
-            for (int e = 0; e < ME; ++e) {
-                if (e >= ne || !((mask >> e) & 1u)) continue;
-                b0 = min_drop_nan(b0, ray_sphere_fast_nan(T[e].x, T[e].y, C[e], dc0, ds0));
-                b1 = min_drop_nan(b1, ray_sphere_fast_nan(T[e].x, T[e].y, C[e], dc1, ds1));
-            }
-            S[w][row + col + r] = b0;
-            S[w][row + col + r + 1] = b1;
-        }
-        if (r < nr) {
-            float dc, ds;
-            sc(S[w][row + col + r], ds, dc);
-            float best = mr;
-#pragma unroll
-            for (int e = 0; e < ME; ++e) {
-                if (e >= ne || !((mask >> e) & 1u)) continue;
-                best = min_drop_nan(best, ray_sphere_fast_nan(T[e].x, T[e].y, C[e], dc, ds));
-            }
-            S[w][row + col + r] = best;
-        }
-        float* lid = io.lidar[s][a] + (long)g0 * nr;
-        for (int k = lane; k < nv * nr; k += 64) {
-            const int e = k / nr;
-            lid[k] = S[w][e * W + col + (k - e * nr)];
-        }
+        lidar_row<RayHardware, false, RM, 2>(
+            S[w] + row + col, nr, [&](int r) { return ang[(long)r * as1] + rot; }, T, C, io.max_range[s],
+            [&](int e) { return e < ne && ((mask >> e) & 1u); });
+        rows_out(S[w], nv, W, nullptr, 0, 0, nullptr, io.lidar[s][a] + (long)g0 * nr, col, nr, lane);
         col += nr;
     }
-    float* obs = moved(io.obs[a], load_out_delta(io).obs) + (long)g0 * W;
-    for (int k = lane; k < nv * W; k += 64) obs[k] = S[w][k];
+    rows_out(S[w], nv, W, moved(io.obs[a], load_out_delta(io).obs) + (long)g0 * W, lane, 64, nullptr, nullptr, 0, 0, lane);
 }
 
 // The same program with a wave per (64 envs, agent, LIDAR) instead of per (64 envs, agent): L
@@ -1112,12 +883,12 @@ __global__ void __launch_bounds__(256) k_discovery_obs_fast(VmasDiscoveryIO io_a
 // 2 per SIMD, too few to hide the trig / sqrt / LDS latencies; this runs 4 096.
 template <int L>
 __global__ void __launch_bounds__(256) k_discovery_obs_split(VmasDiscoveryIO io_arg) {
-    VMAS_KARG(KDiscoveryIO, io_arg);
+    VMAS_PROGRAM_ARGS(VmasDiscoveryIO, io_arg);
     constexpr int ME = kDiscFastEntities, RM = kDiscFastRays, AP = 4 / L;
     __shared__ float S[AP][64 * kDiscFastW];
     const int lane = (int)(threadIdx.x & 63u), w = (int)(threadIdx.x >> 6);
     const int sub = w / L, s = w - sub * L;
-    const int a = __builtin_amdgcn_readfirstlane((int)blockIdx.y * AP + sub);
+    const int a = wave_uniform((int)blockIdx.y * AP + sub);
     const bool active = a < io.n_agents;  // (no early return: the barrier below)
     const int g0 = (int)blockIdx.x * 64, b = g0 + lane;
     const bool valid = b < io.batch;
@@ -1152,64 +923,25 @@ __global__ void __launch_bounds__(256) k_discovery_obs_split(VmasDiscoveryIO io_
         }
         const uint32_t mask = io.mask[s] & ~(1u << self);  // World.cast_rays skips the entity itself
         const int nr = io.n_rays[s];
-        const float mr = io.max_range[s];
         const float* ang = io.angles[s][a] + (long)bb * io.ang_s0[s][a];
         const int as1 = io.ang_s1[s][a];
-#pragma unroll
-        for (int r = 0; r < RM; ++r)
-            if (r < nr) S[sub][row + col + r] = ang[(long)r * as1] + rot;
-        auto sc = [](float th, float& ds, float& dc) {
-            if (fabsf(th) < kFastTrigMaxAngle) {
-                ds = __sinf(th);
-                dc = __cosf(th);
-            } else {
-                sincosf(th, &ds, &dc);
-            }
-        };
-        int r = 0;
-#pragma unroll 1
-        for (; r + 1 < nr; r += 2) {
-            float dc0, ds0, dc1, ds1;
-            sc(S[sub][row + col + r], ds0, dc0);
-            sc(S[sub][row + col + r + 1], ds1, dc1);
-            float b0 = mr, b1 = mr;
-#pragma unroll
-            for (int e = 0; e < ME; ++e) {
-                if (e >= ne || !((mask >> e) & 1u)) continue;
-                b0 = min_drop_nan(b0, ray_sphere_fast_nan(T[e].x, T[e].y, C[e], dc0, ds0));
-                b1 = min_drop_nan(b1, ray_sphere_fast_nan(T[e].x, T[e].y, C[e], dc1, ds1));
-            }
-            S[sub][row + col + r] = b0;
-            S[sub][row + col + r + 1] = b1;
-        }
-        if (r < nr) {
-            float dc, ds;
-            sc(S[sub][row + col + r], ds, dc);
-            float best = mr;
-#pragma unroll
-            for (int e = 0; e < ME; ++e) {
-                if (e >= ne || !((mask >> e) & 1u)) continue;
-                best = min_drop_nan(best, ray_sphere_fast_nan(T[e].x, T[e].y, C[e], dc, ds));
-            }
-            S[sub][row + col + r] = best;
-        }
-        float* lid = io.lidar[s][a] + (long)g0 * nr;  // (this wave's own columns: no barrier needed)
-        for (int k = lane; k < nv * nr; k += 64) {
-            const int e = k / nr;
-            lid[k] = S[sub][e * W + col + (k - e * nr)];
-        }
+        lidar_row<RayHardware, false, RM, 2>(
+            S[sub] + row + col, nr, [&](int r) { return ang[(long)r * as1] + rot; }, T, C, io.max_range[s],
+            [&](int e) { return e < ne && ((mask >> e) & 1u); });
+        // (this wave's own columns: no barrier needed)
+        rows_out(S[sub], nv, W, nullptr, 0, 0, nullptr, io.lidar[s][a] + (long)g0 * nr, col, nr, lane);
     }
     __syncthreads();
     if (!active) return;
-    float* obs = moved(io.obs[a], load_out_delta(io).obs) + (long)g0 * W;
-    for (int k = lane + s * 64; k < nv * W; k += 64 * L) obs[k] = S[sub][k];
+    rows_out(S[sub], nv, W, moved(io.obs[a], load_out_delta(io).obs) + (long)g0 * W, lane + s * 64, 64 * L, nullptr, nullptr,
+             0, 0, lane);
 }
 
 // ---- sampling (sampling.py `sample` / `reward` / `observation` / `nomrlize_pdf`; restated in
 // scenarios/sampling.py) ---------------------------------------------------------------------------
 // The per-(env, agent) program and the grid-point density are host / device functions: the kernels
 // below and the host backend (device == -1) run the same statements.  IO is the argument block by
-// reference -- on the device read in place from the kernel argument segment (see k_flocking_fast).
+// reference -- on the device read in place from the kernel argument segment (VMAS_PROGRAM_ARGS).
 #define VMAS_SAMP_HD __host__ __device__ __forceinline__
 constexpr int kSampMA = VMAS_SAMPLING_MAX_AGENTS, kSampMG = VMAS_SAMPLING_MAX_GAUSSIANS;
 
@@ -1381,15 +1113,19 @@ VMAS_SAMP_HD void samp_agent(IO& io, long b, int k, float* o, float* lid, long l
             const float a = ang[r * as1] + rot;
             float best = mr;
 #ifdef __HIP_DEVICE_COMPILE__
-            if (io.fast_lidar) {
-                float ds, dc;
-                nav_sincos(a, ds, dc);
-#pragma unroll
-                for (int j = 0; j < NA; ++j) {
-                    if (j >= n || j == k) continue;
-                    const float rad = io.radius[j];
-                    best = min_drop_nan(best, nav_ray_nan(CX[j] - px, CY[j] - py, rad * rad, dc, ds));
-                }
+            if (io.fast_lidar) {  // (the targets formed per ray, as the exact branch does)
+                Ray<RayPrecise> q(a, mr);
+                cast_rays<RayPrecise, NA>(
+                    [&](int j, float& ux, float& uy, float& c) {
+                        if (j >= n || j == k) return false;
+                        const float rad = io.radius[j];
+                        ux = CX[j] - px;
+                        uy = CY[j] - py;
+                        c = RayPrecise::c(rad * rad, mk(ux, uy));
+                        return true;
+                    },
+                    q);
+                best = q.best;
             } else
 #endif
             {
@@ -1423,29 +1159,16 @@ VMAS_SAMP_HD void samp_agent(IO& io, long b, int k, float* o, float* lid, long l
     }
 }
 
-#ifdef __HIP_DEVICE_COMPILE__
-typedef const VmasSamplingIO __attribute__((address_space(4))) KSamplingIO;  // (see k_flocking_fast)
-typedef const VmasSamplingMaxPdfIO __attribute__((address_space(4))) KSamplingMaxPdfIO;
-#else
-typedef const VmasSamplingIO KSamplingIO;
-typedef const VmasSamplingMaxPdfIO KSamplingMaxPdfIO;
-#endif
-
 // Grid: x = 64-env groups, y = groups of 4 agents; a wave per (64 envs, agent), the observation rows
-// staged in LDS (4 x 64 x W floats, sized by the launch) and written out as contiguous blocks, as
-// k_navigation_fast.  NA: the static bound of the agent loops (4, 8 or 16: the least >= n_agents).
+// staged in LDS (4 x 64 x W floats, sized by the launch), as k_navigation_fast.  NA: the static bound
+// of the agent loops (4, 8 or 16: the least >= n_agents).
 template <int NA>
 __global__ void __launch_bounds__(256) k_sampling(VmasSamplingIO io_arg) {
-#ifdef __HIP_DEVICE_COMPILE__
-    KSamplingIO& io = *(KSamplingIO*)__builtin_amdgcn_kernarg_segment_ptr();
-    (void)io_arg;
-#else
-    KSamplingIO& io = io_arg;
-#endif
+    VMAS_PROGRAM_ARGS(VmasSamplingIO, io_arg);
     extern __shared__ float samp_lds[];
     const int lane = (int)(threadIdx.x & 63u), w = (int)(threadIdx.x >> 6);
     const int g0 = (int)blockIdx.x * 64, b = g0 + lane;
-    const int k = __builtin_amdgcn_readfirstlane((int)blockIdx.y * 4 + w);
+    const int k = wave_uniform((int)blockIdx.y * 4 + w);
     if (k >= io.n_agents) return;  // (wave-uniform; no workgroup barrier below)
     const bool valid = b < io.batch;
     const int nr = io.lidar_on ? io.n_rays : 0, W = 12 + nr;
@@ -1458,27 +1181,14 @@ __global__ void __launch_bounds__(256) k_sampling(VmasSamplingIO io_arg) {
     if (valid) samp_agent<NA>(io, (long)b, k, S + lane * W, nullptr, od.rew);
     __builtin_amdgcn_wave_barrier();
     const int nv = io.batch - g0 < 64 ? io.batch - g0 : 64;
-    float* obs = moved(io.obs[k], od.obs) + (long)g0 * W;
-    for (int i = lane; i < nv * W; i += 64) obs[i] = S[i];
-    if (nr > 0) {
-        float* lid = io.lidar[k] + (long)g0 * nr;
-        for (int i = lane; i < nv * nr; i += 64) {
-            const int e = i / nr;
-            lid[i] = S[e * W + 4 + (i - e * nr)];
-        }
-    }
+    rows_out(S, nv, W, moved(io.obs[k], od.obs) + (long)g0 * W, lane, 64, nullptr, io.lidar[k] + (long)g0 * nr, 4, nr, lane);
 }
 
 // nomrlize_pdf: a wave per env, lanes over the grid points, then the wave's maximum (order-free).
 __global__ void __launch_bounds__(256) k_sampling_max_pdf(VmasSamplingMaxPdfIO io_arg) {
-#ifdef __HIP_DEVICE_COMPILE__
-    KSamplingMaxPdfIO& io = *(KSamplingMaxPdfIO*)__builtin_amdgcn_kernarg_segment_ptr();
-    (void)io_arg;
-#else
-    KSamplingMaxPdfIO& io = io_arg;
-#endif
+    VMAS_PROGRAM_ARGS(VmasSamplingMaxPdfIO, io_arg);
     const int lane = (int)(threadIdx.x & 63u), w = (int)(threadIdx.x >> 6);
-    const int b = __builtin_amdgcn_readfirstlane((int)blockIdx.x * 4 + w);
+    const int b = wave_uniform((int)blockIdx.x * 4 + w);
     if (b >= io.batch) return;
     if (io.mask && !io.mask[b]) return;
     const int ny = io.n_ys, P = io.n_xs * ny;
