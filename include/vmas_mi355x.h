@@ -52,8 +52,10 @@ extern "C" {
  * v11: VmasTransportIO rew_attr
  * v12: VmasActionProgramRef / vmas_action_programs, VmasVelocityPidRef / vmas_velocity_pid
  * v13: VmasSamplingIO / vmas_sampling_outputs, VmasSamplingMaxPdfIO / vmas_sampling_max_pdf
- * v14: VmasResetDerived / VmasSpawnResetIO / vmas_spawn_reset */
-#define VMAS_ABI_VERSION 14
+ * v14: VmasResetDerived / VmasSpawnResetIO / vmas_spawn_reset
+ * v15: VmasSpawnResetIO fixed-source writes (write_slot < 0), the separation list (n_sep / sep_*) and
+ *      VMAS_RESET_D_MEAN_SQ_SEP / VMAS_RESET_D_ZERO32; VmasSamplingResetIO / vmas_sampling_reset */
+#define VMAS_ABI_VERSION 15
 
 /* error codes */
 #define VMAS_OK 0
@@ -1233,6 +1235,16 @@ int32_t vmas_balance_reset(int32_t device, const VmasBalanceResetIO* io, uint64_
  * force[a] / torque[a] get zeros, steps[b] = 0, and every VmasResetDerived record is evaluated with
  * the fused step programs' arithmetic (csrc/vmas_programs.hpp).
  *
+ * A position code (write_slot[w], sep_slot[j]) is a placed slot s >= 0 or, negative, -1 - j: the fixed
+ * position fixed[j], j < n_fixed -- an entity the reset sets to a given position without placing it
+ * (flocking's scripted target, which is also occupied from the start).
+ *
+ * The separation list (v15; flocking.py `reset_world_at`: distance_shaping): sep_slot[0 .. n_sep) are
+ * the position codes of world.agents, in order.  A VMAS_RESET_D_MEAN_SQ_SEP record of list entry a is
+ * out[b] = mean over the other entries j of (|p_a - p_j| - sep_desired)^2, times factor, summed in the
+ * order of torch's .mean(-1) (sep_sum_mode: the accumulator count, simulator/_fused.py reduce_order)
+ * by the device function the flocking step program uses (csrc/vmas_programs.hpp flock_mean_sq_sep).
+ *
  * The call then copies the words to the host and waits for the stream once.  *increment: what the
  * full reset advances the generator by (the caller adds it, unless *unresolved != 0: then nothing
  * was written and the caller redoes the reset another way from the same generator state). */
@@ -1246,12 +1258,15 @@ int32_t vmas_balance_reset(int32_t device, const VmasBalanceResetIO* io, uint64_
 #define VMAS_RESET_D_NORM 1       /* out[b] = |slot a - slot b| * factor (torch.linalg.vector_norm, dim 2) */
 #define VMAS_RESET_D_BOX_SPHERE 2 /* out8[b] = is_overlapping(box length x width at slot a, rot 0; sphere at slot b) */
 #define VMAS_RESET_D_CLEAR8 3     /* out8[b * n .. + n) = 0 */
+#define VMAS_RESET_D_MEAN_SQ_SEP 4 /* out[b] = the separation term of list entry a, times factor (see above) */
+#define VMAS_RESET_D_ZERO32 5     /* out[b] = 0.f (a float row: CLEAR8 is for bool rows) */
+#define VMAS_RESET_MAX_SEP 16     /* entries of the separation list (== VMAS_FLOCK_MAX_AGENTS) */
 typedef struct VmasResetDerived {
-    int32_t kind, a, b, n; /* VMAS_RESET_D_*; scratch slots; CLEAR8: bytes per row */
-    float factor;          /* NORM */
+    int32_t kind, a, b, n; /* VMAS_RESET_D_*; scratch slots (MEAN_SQ_SEP: a = the list entry); CLEAR8: bytes per row */
+    float factor;          /* NORM, MEAN_SQ_SEP */
     float length, width;   /* BOX_SPHERE: f32 of the box's sizes */
     float radius_lmd;      /* BOX_SPHERE: the sphere's VmasShapeRef.radius_lmd */
-    VmasMutVec out;        /* NORM: [B] */
+    VmasMutVec out;        /* NORM, MEAN_SQ_SEP, ZERO32: [B] */
     uint8_t* out8;         /* BOX_SPHERE: [B] torch.bool contiguous; CLEAR8: [B, n] contiguous */
 } VmasResetDerived;
 typedef struct VmasSpawnResetIO {
@@ -1265,10 +1280,13 @@ typedef struct VmasSpawnResetIO {
     int32_t* words;                       /* VMAS_RESET_WORDS int32 (zeroed by the call's first kernel) */
     float* steps;                         /* [B] contiguous, or NULL */
     VmasVec fixed[VMAS_RESET_MAX_FIXED];  /* [B, 2]: occupied before the first placement */
-    int32_t write_slot[VMAS_RESET_MAX_WRITE];
+    int32_t write_slot[VMAS_RESET_MAX_WRITE]; /* position codes */
     VmasResetEntity write[VMAS_RESET_MAX_WRITE];
     VmasMutVec force[VMAS_RESET_MAX_AGENTS], torque[VMAS_RESET_MAX_AGENTS];
     VmasResetDerived derived[VMAS_RESET_MAX_DERIVED];
+    int32_t n_sep, sep_sum_mode;          /* the separation list (0 entries: none); a power of two <= VMAS_RESET_MAX_SEP */
+    float sep_desired, pad0;              /* f32(desired_distance) */
+    int32_t sep_slot[VMAS_RESET_MAX_SEP]; /* position codes of world.agents, in order */
 } VmasSpawnResetIO;
 int32_t vmas_spawn_reset(int32_t device, const VmasSpawnResetIO* io, uint64_t* increment, int32_t* unresolved,
                          void* stream);
@@ -1359,6 +1377,42 @@ typedef struct VmasSamplingMaxPdfIO {
     float* max_pdf; /* [B] contiguous, in place */
 } VmasSamplingMaxPdfIO;
 int32_t vmas_sampling_max_pdf(int32_t device, const VmasSamplingMaxPdfIO* io, void* stream);
+
+/* vmas_sampling_reset (v15) <- sampling.py `reset_world_at(None)` after World.reset, for the rows of a
+ * mask, in place, in ONE launch and with no host wait (a wave per env; a wave outside the mask reads
+ * its mask byte only).  For a masked env b, in the full reset's order:
+ *   1. the Gaussians' locations: density.loc[g][b] = (column 2g, column 2g + 1) -- WRITTEN by the call,
+ *      and handed to the other lanes of the wave in registers;
+ *   2. max_pdf[b] = the largest unnormalised density over the grid points (xs[i], ys[j]), as
+ *      vmas_sampling_max_pdf computes it, and sampled[b] cleared;
+ *   3. agent a: pos = (column 2G + 2a, column 2G + 2a + 1) clamped to the semidims, sample[a][b] = the
+ *      density there (over max_pdf[b] when norm), zero where the drawn point is out of bounds; zero vel
+ *      / rot / ang_vel / force / torque;
+ *   4. steps[b] = 0.
+ * Column j is element b of the uniform_ call on [B, 1] at generator offset `offset` + j * (the
+ * per-call increment), over [lo, hi) = loc_lo / loc_hi[axis] for the Gaussians and spawn_lo /
+ * spawn_hi[axis] for the agents (mode as vmas_uniform_columns).  *increment = (2 * n_gaussians + 2 *
+ * n_agents) calls, known before the launch (the caller adds it).  A device path only (device -1:
+ * VMAS_E_INVALID). */
+typedef struct VmasSamplingResetIO {
+    int32_t batch, n_agents, mode, norm;
+    int32_t n_xs, n_ys;
+    float loc_lo[2], loc_hi[2];     /* f32(-xdim), f32(-ydim); f32(xdim), f32(ydim) */
+    float spawn_lo[2], spawn_hi[2]; /* the agents' spawn ranges (all zero with spawn_same_pos) */
+    uint64_t seed, offset;
+    VmasSamplingGrid grid;
+    VmasSamplingDensity density;    /* loc[g]: [B, 2], written */
+    const float* xs;                /* torch.arange(-xdim, xdim, grid_spacing) */
+    const float* ys;
+    const uint8_t* mask;            /* [B] torch.bool */
+    float* max_pdf;                 /* [B] contiguous */
+    uint8_t* sampled;               /* [B, n_x, n_y] torch.bool contiguous */
+    float* steps;                   /* [B] contiguous, or NULL */
+    VmasResetEntity agents[VMAS_SAMPLING_MAX_AGENTS];
+    VmasMutVec force[VMAS_SAMPLING_MAX_AGENTS], torque[VMAS_SAMPLING_MAX_AGENTS];
+    float* sample[VMAS_SAMPLING_MAX_AGENTS]; /* [B] contiguous: agent.sample, in place */
+} VmasSamplingResetIO;
+int32_t vmas_sampling_reset(int32_t device, const VmasSamplingResetIO* io, uint64_t* increment, void* stream);
 
 #ifdef __cplusplus
 }

@@ -20,9 +20,12 @@ A tree without ``reset_where`` (the parent commit) times only reset and reset_at
 
 Writes profiles/r12/masked_reset/<label>.json and prints the same JSON line.
 
-``--scenario NAME[,NAME...]`` (balance, navigation, transport, discovery) times those scenarios
-instead, ``where_native`` for every one whose class has a ``reset_world_where`` of its own
-(navigation, transport, discovery: vmas_spawn_reset), and writes under profiles/r16/spawn_reset.
+``--scenario NAME[,NAME...]`` (balance, navigation, transport, discovery, flocking, sampling) times
+those scenarios instead, ``where_native`` for every one whose class has a ``reset_world_where`` of its
+own (navigation, transport, discovery, flocking: vmas_spawn_reset; sampling: vmas_sampling_reset), and
+writes under profiles/r16/spawn_reset -- or, when flocking (32 768 envs, 8 agents: the C5 per-GPU shard)
+or sampling (32 768 envs, 3 agents, as tools/sampling_bench.py) is among them, under
+profiles/r17/flock_sampling_reset.
 ``--package-root DIR`` imports the package from DIR, a built checkout of another commit (the parent:
 its ``reset_where`` is the generic path, ``where_generic``), so that the two trees can be run
 alternately on the same calls:
@@ -50,6 +53,8 @@ SCENARIOS = {
     "navigation": dict(envs=32768, kw=dict(n_agents=4), substeps=0),
     "transport": WORKLOADS["transport"],
     "discovery": dict(envs=16384, kw=dict(), substeps=0),  # C4
+    "flocking": dict(envs=32768, kw=dict(n_agents=8), substeps=0),  # the C5 per-GPU shard
+    "sampling": dict(envs=32768, kw=dict(n_agents=3), substeps=0),  # as tools/sampling_bench.py
 }
 DENSITIES = (0.01, 0.1, 1.0)
 
@@ -169,7 +174,9 @@ def main():
         out["package_root"] = args.package_root
     for name in (args.scenario or ([args.only] if args.only else list(WORKLOADS))):
         out[name] = run(args, name)
-    sub = ("r16", "spawn_reset") if args.scenario else ("r12", "masked_reset")
+    sub = ("r12", "masked_reset")
+    if args.scenario:
+        sub = ("r17", "flock_sampling_reset") if {"flocking", "sampling"} & set(args.scenario) else ("r16", "spawn_reset")
     d = Path(args.out) if args.out else ROOT / "profiles" / sub[0] / sub[1]
     d.mkdir(parents=True, exist_ok=True)
     (d / f"{args.label}.json").write_text(json.dumps(out, indent=1) + "\n")

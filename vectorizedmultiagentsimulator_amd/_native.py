@@ -19,7 +19,7 @@ LIB_PATH = Path(os.environ.get("VMAS_LIB_PATH") or Path(__file__).resolve().pare
 
 # ------------------------------------------------------------------------------------------------
 # constants mirrored from include/vmas_mi355x.h
-VMAS_ABI_VERSION = 14
+VMAS_ABI_VERSION = 15
 VMAS_SPHERE, VMAS_BOX, VMAS_LINE = 0, 1, 2
 (
     VMAS_PAIR_JOINT,
@@ -86,6 +86,7 @@ EXPORTED_SYMBOLS = (
     "vmas_navigation_outputs",
     "vmas_sampling_outputs",
     "vmas_sampling_max_pdf",
+    "vmas_sampling_reset",
     "vmas_assert_publish_range",
     "vmas_transport_outputs",
     "vmas_discovery_outputs",
@@ -477,6 +478,8 @@ VMAS_RESET_MAX_DERIVED = 16
 VMAS_RESET_WORDS = 32
 VMAS_RESET_TRIES_LIMIT = 16384
 VMAS_RESET_D_NORM, VMAS_RESET_D_BOX_SPHERE, VMAS_RESET_D_CLEAR8 = 1, 2, 3
+VMAS_RESET_D_MEAN_SQ_SEP, VMAS_RESET_D_ZERO32 = 4, 5
+VMAS_RESET_MAX_SEP = 16
 
 
 class VmasResetDerived(ctypes.Structure):
@@ -497,6 +500,8 @@ class VmasSpawnResetIO(ctypes.Structure):
         ("write", VmasResetEntity * VMAS_RESET_MAX_WRITE),
         ("force", VmasMutVec * VMAS_RESET_MAX_AGENTS), ("torque", VmasMutVec * VMAS_RESET_MAX_AGENTS),
         ("derived", VmasResetDerived * VMAS_RESET_MAX_DERIVED),
+        ("n_sep", _i32), ("sep_sum_mode", _i32), ("sep_desired", _f32), ("pad0", _f32),
+        ("sep_slot", _i32 * VMAS_RESET_MAX_SEP),
     ]
 
 
@@ -590,6 +595,18 @@ class VmasSamplingMaxPdfIO(ctypes.Structure):
         ("batch", _i32), ("n_xs", _i32), ("n_ys", _i32), ("pad0", _i32),
         ("grid", VmasSamplingGrid), ("density", VmasSamplingDensity),
         ("xs", _vp), ("ys", _vp), ("mask", _vp), ("max_pdf", _vp),
+    ]
+
+
+class VmasSamplingResetIO(ctypes.Structure):
+    _fields_ = [
+        ("batch", _i32), ("n_agents", _i32), ("mode", _i32), ("norm", _i32), ("n_xs", _i32), ("n_ys", _i32),
+        ("loc_lo", _f32 * 2), ("loc_hi", _f32 * 2), ("spawn_lo", _f32 * 2), ("spawn_hi", _f32 * 2),
+        ("seed", ctypes.c_uint64), ("offset", ctypes.c_uint64),
+        ("grid", VmasSamplingGrid), ("density", VmasSamplingDensity),
+        ("xs", _vp), ("ys", _vp), ("mask", _vp), ("max_pdf", _vp), ("sampled", _vp), ("steps", _vp),
+        ("agents", VmasResetEntity * _SA), ("force", VmasMutVec * _SA), ("torque", VmasMutVec * _SA),
+        ("sample", _vp * _SA),
     ]
 
 
@@ -820,6 +837,8 @@ def load_library(path: os.PathLike | str | None = None) -> ctypes.CDLL:
     lib.vmas_sampling_outputs.argtypes = [_i32, _vp, _vp]
     lib.vmas_sampling_max_pdf.restype = _i32
     lib.vmas_sampling_max_pdf.argtypes = [_i32, _vp, _vp]
+    lib.vmas_sampling_reset.restype = _i32
+    lib.vmas_sampling_reset.argtypes = [_i32, _vp, ctypes.POINTER(ctypes.c_uint64), _vp]
     lib.vmas_distance_vjp.restype = _i32
     lib.vmas_distance_vjp.argtypes = [_i32, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
     lib.vmas_cast_rays_vjp.restype = _i32

@@ -159,6 +159,62 @@ __device__ __forceinline__ float xdist_spheres(const VmasShapeRef& a, const Vmas
     return (xnorm(ref_pos(a, b) - ref_pos(c, b)) - a.radius) - c.radius;
 }
 
+// ---- a masked reset's stores (vmas_reset.hip; vmas_scenarios.hip k_sampling_reset) ---------------------
+__device__ __forceinline__ void put2(const VmasMutVec& v, int b, float x, float y) {
+    if (!v.p) return;
+    float* p = v.p + (long)b * v.s0;
+    p[0] = x;
+    p[v.s1] = y;
+}
+__device__ __forceinline__ void put1(const VmasMutVec& v, int b, float x) {
+    if (v.p) v.p[(long)b * v.s0] = x;
+}
+// World.reset zeroes every state field; reset_world_at then sets pos (and the line's rot, to 0)
+__device__ __forceinline__ void reset_place(const VmasResetEntity& e, int b, V2 pos) {
+    put2(e.pos, b, pos.x, pos.y);
+    put2(e.vel, b, 0.f, 0.f);
+    put1(e.rot, b, 0.f);
+    put1(e.ang_vel, b, 0.f);
+}
+
+// ---- flocking's separation term ----------------------------------------------------------------------
+// (stack(|p_k - p_j| for j != k) - desired).pow(2).mean(-1) * factor (flocking.py
+// `_mean_sq_dist_error`), for entry k of na positions, pos(j) the position of entry j (called for
+// j < na, j != k only, with j a constant of an unrolled loop).  The n = na - 1 squares are summed in
+// the order of torch's .mean(-1) over a contiguous last dim: sum_mode strided accumulators
+// (acc_i = x_i + x_{i + acc} + ...), combined by an adjacent-pair tree ((a0 + a1) + (a2 + a3)) ...
+// The host probes which accumulator count torch uses on this device for n (simulator/_fused.py
+// reduce_order; measured on MI355X / ROCm 7.2: the largest power of two <= n).  Static register
+// indices only: element n goes to accumulator n % acc, every value >= +0 so 0 + e == e.  Shared by
+// the step program (vmas_scenarios.hip flock_part0) and the masked reset (vmas_reset.hip).
+template <int MA, class Pos>
+__device__ __forceinline__ float flock_mean_sq_sep(int na, int k, V2 pk, Pos&& pos, float desired, float factor,
+                                                   int sum_mode) {
+    float y[MA];
+#pragma unroll
+    for (int i = 0; i < MA; ++i) y[i] = 0.f;
+    int n = 0;
+    const int accm = sum_mode - 1;
+#pragma unroll
+    for (int j = 0; j < MA; ++j) {
+        if (j >= na || j == k) continue;
+        const float d = norm(pk - pos(j)) - desired;
+        const float e = d * d;
+        const int slot = n & accm;
+#pragma unroll
+        for (int i = 0; i < MA; ++i)
+            if (i == slot) y[i] = y[i] + e;
+        ++n;
+    }
+    const int m = n < sum_mode ? n : sum_mode;
+#pragma unroll
+    for (int w = 1; w < MA; w *= 2)
+#pragma unroll
+        for (int i = 0; i + w < MA; i += 2 * w)
+            if (i + w < m) y[i] = y[i] + y[i + w];
+    return (y[0] * (1.f / (float)n)) * factor;
+}
+
 // ---- the programs ------------------------------------------------------------------------------------
 // Each function takes its argument block as a template IO: `const VmasBalanceIO&` through the k_world
 // epilogue's pointer, or -- in the kernels that receive it by value (k_balance, k_transport,

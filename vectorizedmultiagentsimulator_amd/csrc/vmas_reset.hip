@@ -29,22 +29,7 @@ namespace {
 constexpr int kResetThreads = 64;  // (one wave: the masked rows are few, more workgroups spread them)
 static_assert(sizeof(VmasBalanceResetIO) + sizeof(vmas_uniform::DrawGrid) <= 4096, "kernel argument block");
 
-__device__ __forceinline__ void put2(const VmasMutVec& v, int b, float x, float y) {
-    if (!v.p) return;
-    float* p = v.p + (long)b * v.s0;
-    p[0] = x;
-    p[v.s1] = y;
-}
-__device__ __forceinline__ void put1(const VmasMutVec& v, int b, float x) {
-    if (v.p) v.p[(long)b * v.s0] = x;
-}
-// World.reset zeroes every state field; reset_world_at then sets pos (and the line's rot, to 0)
-__device__ __forceinline__ void place(const VmasResetEntity& e, int b, V2 pos) {
-    put2(e.pos, b, pos.x, pos.y);
-    put2(e.vel, b, 0.f, 0.f);
-    put1(e.rot, b, 0.f);
-    put1(e.ang_vel, b, 0.f);
-}
+// (put1 / put2 / reset_place: vmas_programs.hpp, shared with vmas_scenarios.hip k_sampling_reset)
 
 __global__ void __launch_bounds__(kResetThreads) k_balance_reset(VmasBalanceResetIO io_arg, vmas_uniform::DrawGrid g) {
     VMAS_PROGRAM_ARGS(VmasBalanceResetIO, io_arg);
@@ -61,26 +46,26 @@ __global__ void __launch_bounds__(kResetThreads) k_balance_reset(VmasBalanceRese
     const V2 pf = mk(io.floor_x, io.floor_y);
     for (int i = 0; i < io.n_agents; ++i) {
         const VmasResetEntity ag = io.agents[i];
-        place(ag, b, mk(line.x + io.agent_dx[i], line.y + io.agent_dy));  // line_pos + offset
+        reset_place(ag, b, mk(line.x + io.agent_dx[i], line.y + io.agent_dy));  // line_pos + offset
         const VmasMutVec f = io.force[i], t = io.torque[i];
         put2(f, b, 0.f, 0.f);
         put1(t, b, 0.f);
     }
     {
         const VmasResetEntity e = io.goal;
-        place(e, b, goal);
+        reset_place(e, b, goal);
     }
     {
         const VmasResetEntity e = io.package;
-        place(e, b, pkg);
+        reset_place(e, b, pkg);
     }
     {
         const VmasResetEntity e = io.line;
-        place(e, b, line);
+        reset_place(e, b, line);
     }
     {
         const VmasResetEntity e = io.floor;
-        place(e, b, pf);
+        reset_place(e, b, pf);
     }
     // compute_on_the_ground: is_overlapping(line, floor) + is_overlapping(package, floor), as
     // bal_side / bal_reward compute it (every rot is 0 after the reset)
@@ -139,6 +124,7 @@ struct PlaceArgs {
 static_assert(sizeof(PlaceArgs) + sizeof(vmas_uniform::DrawGrid) <= 4096, "kernel argument block");
 static_assert(sizeof(VmasSpawnResetIO) <= 4096, "kernel argument block");
 static_assert(VMAS_RESET_MAX_PLACE < VMAS_RESET_WORDS, "the unresolved word");
+static_assert(VMAS_RESET_MAX_SEP == VMAS_FLOCK_MAX_AGENTS, "the step program's accumulators");
 
 // torch.cdist(...) < min_dist as d2 < d2_min (vmas_spawn.hip near; vmas_aux.hpp spawn_d2_min)
 __device__ __forceinline__ bool too_near(float ox, float oy, float x, float y, float d2_min) {
@@ -209,9 +195,15 @@ __global__ void __launch_bounds__(kResetThreads) k_reset_commit(VmasSpawnResetIO
     if (io.words[VMAS_RESET_MAX_PLACE] != 0) return;  // (nothing has been written: the placement wrote scratch only)
     const float* S = io.scratch;
     auto slot = [&](int s) { return mk(S[(size_t)(2 * s) * B + b], S[(size_t)(2 * s + 1) * B + b]); };
+    // a position code: a placed slot, or -1 - j for the fixed position j (validated by the host)
+    auto at = [&](int s) {
+        if (s >= 0) return slot(s);
+        const VmasVec v = io.fixed[-1 - s];
+        return ld_vec2(v, b);
+    };
     for (int w = 0; w < io.n_write; ++w) {
         const VmasResetEntity e = io.write[w];
-        place(e, b, slot(io.write_slot[w]));
+        reset_place(e, b, at(io.write_slot[w]));
     }
     for (int a = 0; a < io.n_agents; ++a) {
         const VmasMutVec f = io.force[a], t = io.torque[a];
@@ -232,6 +224,14 @@ __global__ void __launch_bounds__(kResetThreads) k_reset_commit(VmasSpawnResetIO
             r.out8[b] = ((dsb < dcb) || (dsc < r.radius_lmd)) ? 1 : 0;
         } else if (r.kind == VMAS_RESET_D_CLEAR8) {
             for (int k = 0; k < r.n; ++k) r.out8[(size_t)b * r.n + k] = 0;
+        } else if (r.kind == VMAS_RESET_D_MEAN_SQ_SEP) {
+            // flocking's distance_shaping from the new positions: the step program's own function
+            put1(r.out, b,
+                 flock_mean_sq_sep<VMAS_RESET_MAX_SEP>(
+                     io.n_sep, r.a, at(io.sep_slot[r.a]), [&](int j) { return at(io.sep_slot[j]); }, io.sep_desired,
+                     r.factor, io.sep_sum_mode));
+        } else if (r.kind == VMAS_RESET_D_ZERO32) {
+            put1(r.out, b, 0.f);
         }
     }
 }
@@ -278,16 +278,28 @@ extern "C" int32_t vmas_spawn_reset(int32_t device, const VmasSpawnResetIO* io, 
                               io->batch, io->n_place, io->n_write);
     for (int j = 0; j < io->n_fixed; ++j)
         if (!io->fixed[j].p) return vmas_aux::fail(VMAS_E_INVALID, "vmas_spawn_reset: null fixed position %d", j);
+    // a position code: a placed slot, or -1 - j for fixed[j]
+    auto code_ok = [&](int32_t c) { return c >= 0 ? c < io->n_place : -1 - (long)c < (long)io->n_fixed; };
     for (int w = 0; w < io->n_write; ++w)
-        if (io->write_slot[w] < 0 || io->write_slot[w] >= io->n_place)
-            return vmas_aux::fail(VMAS_E_INVALID, "vmas_spawn_reset: entity %d reads slot %d of %d", w, io->write_slot[w],
-                                  io->n_place);
+        if (!code_ok(io->write_slot[w]))
+            return vmas_aux::fail(VMAS_E_INVALID, "vmas_spawn_reset: entity %d reads slot %d of %d (%d fixed)", w,
+                                  io->write_slot[w], io->n_place, io->n_fixed);
+    if (io->n_sep < 0 || io->n_sep > VMAS_RESET_MAX_SEP)
+        return vmas_aux::fail(VMAS_E_INVALID, "vmas_spawn_reset: a separation list of %d", io->n_sep);
+    for (int j = 0; j < io->n_sep; ++j)
+        if (!code_ok(io->sep_slot[j]))
+            return vmas_aux::fail(VMAS_E_INVALID, "vmas_spawn_reset: separation entry %d reads slot %d of %d (%d fixed)", j,
+                                  io->sep_slot[j], io->n_place, io->n_fixed);
+    const bool sep_ok = io->n_sep >= 2 && io->sep_sum_mode >= 1 && io->sep_sum_mode <= VMAS_RESET_MAX_SEP &&
+                        !(io->sep_sum_mode & (io->sep_sum_mode - 1));
     for (int d = 0; d < io->n_derived; ++d) {
         const VmasResetDerived& r = io->derived[d];
         const bool slots = r.a >= 0 && r.a < io->n_place && r.b >= 0 && r.b < io->n_place;
         const bool ok = r.kind == VMAS_RESET_D_NORM         ? slots && r.out.p
                         : r.kind == VMAS_RESET_D_BOX_SPHERE ? slots && r.out8
                         : r.kind == VMAS_RESET_D_CLEAR8     ? r.out8 && r.n >= 0
+                        : r.kind == VMAS_RESET_D_MEAN_SQ_SEP ? sep_ok && r.a >= 0 && r.a < io->n_sep && r.out.p
+                        : r.kind == VMAS_RESET_D_ZERO32     ? r.out.p != nullptr
                                                             : false;
         if (!ok) return vmas_aux::fail(VMAS_E_INVALID, "vmas_spawn_reset: derived value %d (kind %d)", d, r.kind);
     }

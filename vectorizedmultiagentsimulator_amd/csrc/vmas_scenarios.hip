@@ -16,6 +16,7 @@
 #include "vmas_mi355x.h"
 #include "vmas_programs.hpp"
 #include "vmas_query.hpp"
+#include "vmas_uniform.hpp"
 
 using namespace vmas;
 
@@ -59,10 +60,8 @@ __global__ void __launch_bounds__(256) k_balance(VmasBalanceIO io_arg) {
 }
 
 // The flocking separation term sums n floats in the order of torch's .mean(-1) over a contiguous
-// last dim: `acc` strided accumulators (acc_i = x_i + x_{i+acc} + ...), combined by an
-// adjacent-pair tree ((a0+a1)+(a2+a3))...  The host probes which accumulator count torch uses on
-// this device for n (simulator/_fused.py reduce_order; measured on MI355X / ROCm 7.2: the largest
-// power of two <= n) and passes it as sum_mode.
+// last dim (vmas_programs.hpp flock_mean_sq_sep, shared with the masked reset; sum_mode: the
+// accumulator count the host probed, simulator/_fused.py reduce_order).
 
 // flocking.py:149-206 (restated in scenarios/flocking.py).  Grid: x = 64-env groups, y = (policy
 // agent p, part): part 0 is p's reward and the first six observation entries, part 1 + r is ray r
@@ -109,31 +108,9 @@ __device__ __forceinline__ FlockHead flock_part0(IO& io, int b, int p, const Out
             cr = io.collision_rew[p][b];
         }
         // separation: (stack(|p_k - p_j| for j != k) - desired).pow(2).mean(-1) * factor, summed
-        // in torch's order (static register indices: element n goes to accumulator n % acc, every
-        // value >= +0 so 0 + e == e)
-        float y[MA];
-#pragma unroll
-        for (int i = 0; i < MA; ++i) y[i] = 0.f;
-        int n = 0;
-        const int accm = io.sum_mode - 1;
-#pragma unroll
-        for (int j = 0; j < MA; ++j) {
-            if (j >= na || j == k) continue;
-            const float d = norm(pk - P[j]) - io.desired_distance;
-            const float e = d * d;
-            const int slot = n & accm;
-#pragma unroll
-            for (int i = 0; i < MA; ++i)
-                if (i == slot) y[i] = y[i] + e;
-            ++n;
-        }
-        const int m = n < io.sum_mode ? n : io.sum_mode;
-#pragma unroll
-        for (int w = 1; w < MA; w *= 2)
-#pragma unroll
-            for (int i = 0; i + w < MA; i += 2 * w)
-                if (i + w < m) y[i] = y[i] + y[i + w];
-        const float shaping = (y[0] * (1.f / (float)n)) * io.dist_shaping_factor;
+        // in torch's order (vmas_programs.hpp)
+        const float shaping = flock_mean_sq_sep<MA>(
+            na, k, pk, [&](int j) { return P[j]; }, io.desired_distance, io.dist_shaping_factor, io.sum_mode);
         const float dr = io.shaping_in[p][b] - shaping;
         io.shaping_out[p][b] = shaping;
         io.dist_rew[p][b] = dr;
@@ -984,6 +961,15 @@ VMAS_SAMP_HD float samp_acc_tree(float* y, int n, int acc) {
             if (i + w < m) y[i] = y[i] + y[i + w];
     return y[0];
 }
+// Gaussian g's term of the density at (x, y), its location (lx, ly) given
+template <class IO>
+VMAS_SAMP_HD float samp_term(IO& io, int g, float x, float y, float lx, float ly) {
+    const float L = io.density.scale[g];
+    const float y0 = (x - lx) / L, y1 = (y - ly) / L;
+    const float M = y0 * y0 + y1 * y1;
+    const float lg = (-0.5f * (io.density.log_norm + M)) - io.density.half_log_det[g];
+    return expf(lg);
+}
 // the unnormalised density of (x, y) in env b (include/vmas_mi355x.h, "sampling")
 template <class IO>
 VMAS_SAMP_HD float samp_density(IO& io, long b, float x, float y) {
@@ -991,25 +977,41 @@ VMAS_SAMP_HD float samp_density(IO& io, long b, float x, float y) {
 #pragma unroll
     for (int i = 0; i < kSampMG; ++i) acc[i] = 0.f;
     const int ng = io.density.n_gaussians, am = io.density.sum_mode - 1;
-    const float c = io.density.log_norm;
 #pragma unroll 1
     for (int g = 0; g < ng; ++g) {
         const float* lp = io.density.loc[g].p;
         const long s0 = io.density.loc[g].s0, s1 = io.density.loc[g].s1;
-        const float L = io.density.scale[g];
-        const float y0 = (x - lp[b * s0]) / L, y1 = (y - lp[b * s0 + s1]) / L;
-        const float M = y0 * y0 + y1 * y1;
-        const float lg = (-0.5f * (c + M)) - io.density.half_log_det[g];
-        samp_acc_add<kSampMG>(acc, g & am, expf(lg));
+        samp_acc_add<kSampMG>(acc, g & am, samp_term(io, g, x, y, lp[b * s0], lp[b * s0 + s1]));
     }
     return samp_acc_tree<kSampMG>(acc, ng, io.density.sum_mode);
 }
-// sample(p, norm=False) of a grid point of nomrlize_pdf (the flags were cleared just before)
+// The same with the env's locations by value (k_sampling_reset: drawn by this wave, held in
+// registers -- the loop is unrolled so that every index is static).
+struct SampLocs {
+    float x[kSampMG], y[kSampMG];
+};
+template <class IO>
+VMAS_SAMP_HD float samp_density_at(IO& io, const SampLocs& l, float x, float y) {
+    float acc[kSampMG];
+#pragma unroll
+    for (int i = 0; i < kSampMG; ++i) acc[i] = 0.f;
+    const int ng = io.density.n_gaussians, am = io.density.sum_mode - 1;
+#pragma unroll
+    for (int g = 0; g < kSampMG; ++g)
+        if (g < ng) samp_acc_add<kSampMG>(acc, g & am, samp_term(io, g, x, y, l.x[g], l.y[g]));
+    return samp_acc_tree<kSampMG>(acc, ng, io.density.sum_mode);
+}
+// sample(p, norm=False) of a grid point of nomrlize_pdf (the flags were cleared just before);
+// density(x, y): the env's density at a clamped point
+template <class IO, class D>
+VMAS_SAMP_HD float samp_grid_point_of(IO& io, float x, float y, D&& density) {
+    const bool oob = samp_oob(io, x, y);
+    const float v = density(samp_clamp(x, io.grid.x_semidim), samp_clamp(y, io.grid.y_semidim));
+    return oob ? 0.f : v;
+}
 template <class IO>
 VMAS_SAMP_HD float samp_grid_point(IO& io, long b, float x, float y) {
-    const bool oob = samp_oob(io, x, y);
-    const float v = samp_density(io, b, samp_clamp(x, io.grid.x_semidim), samp_clamp(y, io.grid.y_semidim));
-    return oob ? 0.f : v;
+    return samp_grid_point_of(io, x, y, [&](float cx, float cy) { return samp_density(io, b, cx, cy); });
 }
 
 // Agent k in env b.  REWARD (k == 0 only; the reward block of every agent): flags are read before any
@@ -1200,6 +1202,76 @@ __global__ void __launch_bounds__(256) k_sampling_max_pdf(VmasSamplingMaxPdfIO i
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) m = samp_max(m, __shfl_xor(m, off, 64));
     if (lane == 0) io.max_pdf[b] = m;
+}
+
+// sampling.py `reset_world_at(None)` after World.reset for the envs of a mask (include/vmas_mi355x.h
+// vmas_sampling_reset has the order).  A wave per env, as k_sampling_max_pdf; a wave whose env is
+// outside the mask returns before any cross-lane operation (the test is wave-uniform) having read its
+// mask byte only.  Lane l < 2 G + 2 A draws column l of the call (uniform_at: element b of the full
+// reset's uniform_ call on [B, 1]); the Gaussians' locations reach every lane by readlane, never by a
+// store another lane loads back -- `_locs` is written as a side effect.  Lanes then stride the grid
+// points for the maximum and the flag row to clear it; the first A lanes do the agents.
+__global__ void __launch_bounds__(256) k_sampling_reset(VmasSamplingResetIO io_arg, vmas_uniform::DrawGrid dg) {
+    VMAS_PROGRAM_ARGS(VmasSamplingResetIO, io_arg);
+    const int lane = (int)(threadIdx.x & 63u), w = (int)(threadIdx.x >> 6);
+    const int b = wave_uniform((int)blockIdx.x * 4 + w);
+    if (b >= io.batch || io.mask[b] == 0) return;
+    const int ng = io.density.n_gaussians, na = io.n_agents;
+    // 1. every draw of the env: columns [0, 2 G) the locations, [2 G, 2 G + 2 A) the agents' spawns
+    const bool is_loc = lane < 2 * ng, y_axis = (lane & 1) != 0;
+    const float lo = is_loc ? (y_axis ? io.loc_lo[1] : io.loc_lo[0]) : (y_axis ? io.spawn_lo[1] : io.spawn_lo[0]);
+    const float hi = is_loc ? (y_axis ? io.loc_hi[1] : io.loc_hi[0]) : (y_axis ? io.spawn_hi[1] : io.spawn_hi[0]);
+    float u = 0.f;
+    if (lane < 2 * (ng + na))
+        u = vmas_uniform::uniform_at(io.seed, io.offset + dg.inc * (unsigned long long)lane, dg, b, lo, hi, io.mode);
+    SampLocs L;
+#pragma unroll
+    for (int g = 0; g < kSampMG; ++g) {
+        L.x[g] = __shfl(u, 2 * g, 64);
+        L.y[g] = __shfl(u, 2 * g + 1, 64);
+        if (g < ng && (lane >> 1) == g) {
+            const VmasVec v = io.density.loc[g];
+            const_cast<float*>(v.p)[(long)b * v.s0 + (y_axis ? v.s1 : 0)] = u;
+        }
+    }
+    const int src = 2 * ng + 2 * (lane < na ? lane : 0);
+    const float sx = __shfl(u, src, 64), sy = __shfl(u, src + 1, 64);
+    // 2. nomrlize_pdf: max_pdf[b] = 0, then the maximum over the grid points (order-free)
+    const int ny = io.n_ys, P = io.n_xs * ny;
+    float m = 0.f;
+    for (int p = lane; p < P; p += 64) {
+        const int ix = p / ny, iy = p - ix * ny;
+        m = samp_max(m, samp_grid_point_of(io, io.xs[ix], io.ys[iy],
+                                           [&](float cx, float cy) { return samp_density_at(io, L, cx, cy); }));
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) m = samp_max(m, __shfl_xor(m, off, 64));
+    if (lane == 0) {
+        io.max_pdf[b] = m;
+        if (io.steps) io.steps[b] = 0.f;
+    }
+    // sampled[b] = False: 16 bytes per store where the rows allow it
+    const long cells = (long)io.grid.n_x * io.grid.n_y;
+    uint8_t* flags = io.sampled + (long)b * cells;
+    if ((((unsigned long long)cells | (unsigned long long)(uintptr_t)io.sampled) & 15ull) == 0) {
+        uint4* f = reinterpret_cast<uint4*>(flags);
+        for (long i = lane; i < cells / 16; i += 64) f[i] = make_uint4(0u, 0u, 0u, 0u);
+    } else {
+        for (long i = lane; i < cells; i += 64) flags[i] = 0;
+    }
+    // 3. the agents: set_pos(spawn), then sample(pos, norm) -- the clamp in place, zero where the
+    // drawn point is out of bounds (the cell's flag was cleared above)
+    if (lane >= na) return;
+    const bool oob = samp_oob(io, sx, sy);
+    const float cx = samp_clamp(sx, io.grid.x_semidim), cy = samp_clamp(sy, io.grid.y_semidim);
+    float v = samp_density_at(io, L, cx, cy);
+    if (io.norm) v = v / m;
+    const VmasResetEntity e = io.agents[lane];
+    reset_place(e, b, mk(cx, cy));
+    const VmasMutVec f = io.force[lane], t = io.torque[lane];
+    put2(f, b, 0.f, 0.f);
+    put1(t, b, 0.f);
+    io.sample[lane][b] = oob ? 0.f : v;
 }
 
 const char* samp_density_error(const VmasSamplingGrid& g, const VmasSamplingDensity& d) {
@@ -1406,6 +1478,41 @@ int32_t vmas_sampling_max_pdf(int32_t device, const VmasSamplingMaxPdfIO* io, vo
     VMAS_AUX_HIP(hipSetDevice(device));
     hipLaunchKernelGGL(k_sampling_max_pdf, dim3((io->batch + 3) / 4), dim3(256), 0, (hipStream_t)stream, *io);
     VMAS_AUX_HIP(hipGetLastError());
+    return VMAS_OK;
+}
+
+int32_t vmas_sampling_reset(int32_t device, const VmasSamplingResetIO* io, uint64_t* increment, void* stream) {
+    if (!io || !increment) return vmas_aux::fail(VMAS_E_INVALID, "vmas_sampling_reset: null argument block");
+    if (device < 0 || device >= 64)
+        return vmas_aux::fail(VMAS_E_INVALID, "vmas_sampling_reset: device %d (the draws are a device path only)", device);
+    if (io->batch <= 0 || io->n_agents < 1 || io->n_agents > VMAS_SAMPLING_MAX_AGENTS || io->mode < 0 || io->mode > 3 ||
+        io->n_xs <= 0 || io->n_ys <= 0 || (long)io->n_xs * io->n_ys > (1L << 30) || !io->xs || !io->ys || !io->mask ||
+        !io->max_pdf || !io->sampled)
+        return vmas_aux::fail(VMAS_E_INVALID, "vmas_sampling_reset: bad arguments (batch %d, %d agents)", io->batch,
+                              io->n_agents);
+    if (const char* why = samp_density_error(io->grid, io->density))
+        return vmas_aux::fail(VMAS_E_INVALID, "vmas_sampling_reset: bad arguments (%s)", why);
+    for (int i = 0; i < io->n_agents; ++i)
+        if (!io->agents[i].pos.p || !io->sample[i])
+            return vmas_aux::fail(VMAS_E_INVALID, "vmas_sampling_reset: null pointer (agent %d)", i);
+    static_assert(2 * (VMAS_SAMPLING_MAX_GAUSSIANS + VMAS_SAMPLING_MAX_AGENTS) <= 64, "a lane per draw");
+    static_assert(sizeof(VmasSamplingResetIO) + sizeof(vmas_uniform::DrawGrid) <= 4096, "kernel argument block");
+    VMAS_AUX_HIP(hipSetDevice(device));
+    static int max_blocks[64] = {0};
+    if (!max_blocks[device]) {
+        hipDeviceProp_t prop;
+        VMAS_AUX_HIP(hipGetDeviceProperties(&prop, device));
+        max_blocks[device] = prop.multiProcessorCount * (prop.maxThreadsPerMultiProcessor / vmas_uniform::kThreads);
+        if (max_blocks[device] <= 0) return vmas_aux::fail(VMAS_E_HIP, "vmas_sampling_reset: device properties");
+    }
+    // torch's distribution-kernel grid and per-call philox increment on B elements
+    int gx_draw = 0;
+    unsigned long long inc = 0;
+    vmas_uniform::grid_for(io->batch, max_blocks[device], &gx_draw, &inc);
+    const vmas_uniform::DrawGrid g{(long long)vmas_uniform::kThreads * gx_draw, inc};
+    hipLaunchKernelGGL(k_sampling_reset, dim3((io->batch + 3) / 4), dim3(256), 0, (hipStream_t)stream, *io, g);
+    VMAS_AUX_HIP(hipGetLastError());
+    *increment = inc * 2ull * (unsigned long long)(io->density.n_gaussians + io->n_agents);
     return VMAS_OK;
 }
 

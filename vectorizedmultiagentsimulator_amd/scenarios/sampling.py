@@ -144,6 +144,102 @@ class Scenario(BaseScenario):
             agent.set_pos(spawn, batch_index=env_index)
             agent.sample = self.sample(agent.state.pos, norm=self.norm)  # (clamps the spawn in place)
 
+    # ---- masked reset (Environment.reset_where; csrc/vmas_scenarios.hip k_sampling_reset) --------
+    # The rows of `mask` as reset_world_at(None) after World.reset leaves them, written in place by
+    # ONE launch with no host wait: a wave per masked env draws the env's elements of the full reset's
+    # uniform_ columns (the generator advance, 2 per Gaussian and 2 per agent, is known beforehand),
+    # finds max_pdf over the grid points, clears the flag row and places the agents with their
+    # samples.  _undo and _native["undo_live"] are a step's, not a reset's: untouched, as by reset().
+    native_resets = 0  # launches made (a test's proof that no fall-back ran)
+
+    def reset_world_where(self, mask):
+        from vectorizedmultiagentsimulator_amd.simulator.environment import _uniform
+        from vectorizedmultiagentsimulator_amd.simulator.environment._spawn_reset import _mut
+
+        w = self.world
+        env = getattr(self, "_where_env", None)
+        if not _fused.enabled(w) or getattr(w, "_grad_enabled", False):
+            return NotImplemented
+        plan = self._fused_plan()
+        if plan is None or plan["dev"].type != "cuda":
+            return NotImplemented
+        dev, B, agents = plan["dev"], w.batch_dim, w.agents
+        mode = _uniform.mode(dev, B)
+        mp, fl = self.max_pdf, self.sampled
+        if (mode is None or mask.dtype is not torch.bool or mask.device != dev or not mask.is_contiguous()
+                or mp.dtype is not torch.float32 or not mp.is_contiguous() or mp.device != dev or mp.shape != (B,)
+                or fl.dtype is not torch.bool or not fl.is_contiguous() or fl.device != dev
+                or fl.shape != (B, self.n_x_cells, self.n_y_cells)):
+            return NotImplemented
+        steps = env.steps if env is not None else None
+        if steps is not None and (steps.dtype is not torch.float32 or steps.shape != (B,) or not steps.is_contiguous()
+                                  or steps.device != dev):
+            return NotImplemented
+        # (graph mode) a field still bound to the persistent action buffer, whose rows the next step's
+        # actions own, leaves the call to the generic path
+        p_buf = getattr(getattr(env, "_u_persist", None), "buffer", None)
+        p_lo = p_buf.data_ptr() if p_buf is not None else 0
+        p_hi = p_lo + 4 * p_buf.numel() if p_buf is not None else 0
+        io = N.VmasSamplingResetIO()
+        written = [mp, fl, self._locs]
+        ok = True
+
+        def mut(t):
+            nonlocal ok
+            v = _mut(t, dev)
+            if v is None or p_lo <= t.data_ptr() < p_hi:
+                ok = False
+                return N.VmasMutVec()
+            written.append(t)
+            return v
+
+        for i, a in enumerate(agents):
+            st, dst = a.state, io.agents[i]
+            smp = getattr(a, "sample", None)
+            if (st.c is not None or not isinstance(smp, Tensor) or smp.dtype is not torch.float32 or smp.device != dev
+                    or smp.shape != (B,) or not smp.is_contiguous()):
+                return NotImplemented  # (communication state is zeroed by World.reset, not by the launch)
+            dst.pos, dst.vel, dst.rot, dst.ang_vel = mut(st.pos), mut(st.vel), mut(st.rot), mut(st.ang_vel)
+            io.force[i], io.torque[i] = mut(st.__dict__.get("_force")), mut(st.__dict__.get("_torque"))
+            io.sample[i] = smp.data_ptr()
+            written.append(smp)
+        # (one tensor bound to two fields -- a user's set_pos of a shared tensor -- cannot take two rows)
+        if not ok or len({t.data_ptr() for t in written}) != len(written):
+            return NotImplemented
+        points = plan.get("points")
+        if points is None:  # (the grid points of nomrlize_pdf, kept with the plan: two launches less per call)
+            points = plan["points"] = self._grid_points()
+        xpoints, ypoints = points
+        keep = []
+        try:
+            self._fill_density(io.grid, io.density, plan, keep)
+        except _NotFusable:
+            return NotImplemented
+        io.batch, io.n_agents, io.mode, io.norm = B, len(agents), mode, int(bool(self.norm))
+        io.n_xs, io.n_ys = xpoints.numel(), ypoints.numel()
+        for k, (loc, spawn) in enumerate(((self.xdim, self.agent_xspawn_range), (self.ydim, self.agent_yspawn_range))):
+            io.loc_lo[k], io.loc_hi[k] = float(-loc), float(loc)  # (uniform_(-b, b) of _draw_xy)
+            io.spawn_lo[k], io.spawn_hi[k] = float(-spawn), float(spawn)
+        io.xs, io.ys, io.mask = xpoints.data_ptr(), ypoints.data_ptr(), mask.data_ptr()
+        io.max_pdf, io.sampled = mp.data_ptr(), fl.data_ptr()
+        io.steps = steps.data_ptr() if steps is not None else None
+        gen = torch.cuda.default_generators[dev.index]
+        off = gen.get_offset()
+        io.seed, io.offset = gen.initial_seed(), off
+        inc = ctypes.c_uint64(0)
+        _fused.check(_fused.lib().vmas_sampling_reset(dev.index, ctypes.byref(io), ctypes.byref(inc), _fused.stream(w)),
+                     "vmas_sampling_reset")
+        gen.set_offset(off + inc.value)
+        for t in written:
+            _fused.bump_version(t)
+        if steps is not None:
+            _fused.bump_version(steps)
+            self._where_steps_done = True
+        for e in w.entities:
+            e.notify_observers()
+        self.native_resets += 1
+        return None
+
     # ---- the density ----------------------------------------------------------------------------
     def _density(self, pos: Tensor, locs=None) -> Tensor:
         """sum_g exp(MultivariateNormal(loc_g, cov_g I).log_prob(pos)) for pos [..., 2] against locs

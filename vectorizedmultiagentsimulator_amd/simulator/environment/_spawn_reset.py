@@ -1,6 +1,6 @@
 """The native path of ``Environment.reset_where(mask)`` for scenarios whose reset places entities by
 rejection sampling (``ScenarioUtils.spawn_entities_randomly`` / ``find_random_pos_for_entity``):
-navigation, transport, discovery.
+navigation, transport, discovery, flocking.
 
 One ``vmas_spawn_reset`` call (csrc/vmas_reset.hip): a ``k_reset_place`` launch per placed entity --
 the reference's placement loop for EVERY env, since an env outside the mask can hold the batch's
@@ -16,9 +16,14 @@ A scenario describes its reset as
     one hashable per placed position (an entity, or any token for a position that no entity or
     several entities take); a key's scratch slot is its place in that order;
   * ``writes``: ``[(entity, key), ...]`` -- every entity of the world with the key whose position it
-    gets (vel / rot / ang_vel are zeroed as ``World.reset`` zeroes them);
+    gets (vel / rot / ang_vel are zeroed as ``World.reset`` zeroes them); ``Fixed(j)`` in place of a
+    key: the entity is set to ``fixed[j]``, a given position, and not placed (flocking's target);
   * ``derived``: the values ``reset_world_at`` computes from the new positions: ``("norm", key_a,
-    key_b, factor, out)``, ``("box_sphere", box, sphere, key_box, key_sphere, out)``, ``("clear", out)``.
+    key_b, factor, out)``, ``("box_sphere", box, sphere, key_box, key_sphere, out)``, ``("clear", out)``
+    (bool rows), ``("zero", out)`` (a float row), ``("mean_sq_sep", i, factor, out)``: flocking's
+    separation term of entry ``i`` of ``sep``'s list;
+  * ``sep``: ``(positions, desired_distance)`` -- the key or ``Fixed(j)`` of every agent of
+    ``world.agents``, in order (one list per call).
 
 ``spawn_reset_where`` returns ``NotImplemented`` wherever the launch cannot stand in for the full
 reset (the caller then leaves the call to the generic path), as balance's ``reset_world_where`` does.
@@ -53,7 +58,14 @@ def _bool_rows(t, dev, shape) -> bool:
             and t.is_contiguous())
 
 
-def spawn_reset_where(scenario, mask, stages, writes, x_bounds, y_bounds, derived=(), fixed=(), max_tries=0):
+class Fixed:
+    """In place of a key: the position ``fixed[j]``."""
+
+    def __init__(self, j: int):
+        self.j = int(j)
+
+
+def spawn_reset_where(scenario, mask, stages, writes, x_bounds, y_bounds, derived=(), fixed=(), max_tries=0, sep=None):
     """The rows of ``mask`` as the scenario's full reset leaves them, in place (see the module's
     head); ``None`` when done, ``NotImplemented`` when the generic path has to run.  Counts
     ``scenario.native_resets`` (launched and committed) and ``scenario.native_reset_fallbacks`` (an
@@ -81,6 +93,14 @@ def spawn_reset_where(scenario, mask, stages, writes, x_bounds, y_bounds, derive
     if steps is not None and (steps.dtype is not torch.float32 or steps.shape != (B,) or not steps.is_contiguous()
                               or steps.device != dev):
         return NotImplemented
+
+    def code(key):
+        """The ABI's position code: a placed slot, or -1 - j for ``fixed[j]``."""
+        if isinstance(key, Fixed):
+            assert 0 <= key.j < len(fixed), key.j
+            return -1 - key.j
+        return slot_of[key]
+
     # (graph mode) a field still bound to the persistent action buffer, whose rows the next step's
     # actions own, leaves the call to the generic path
     p_buf = getattr(getattr(env, "_u_persist", None), "buffer", None)
@@ -104,10 +124,10 @@ def spawn_reset_where(scenario, mask, stages, writes, x_bounds, y_bounds, derive
     pos_slot = {}  # id(pos tensor) -> the slot it takes
     for i, (e, key) in enumerate(writes):
         st, dst = e.state, io.write[i]
-        io.write_slot[i] = slot_of[key]
+        io.write_slot[i] = code(key)
         # (the full reset binds ONE tensor as the pos of every entity set to the same position --
         # navigation's shared goals: it takes its slot once; another slot would need two rows)
-        if pos_slot.setdefault(id(st.pos), slot_of[key]) != slot_of[key]:
+        if pos_slot.setdefault(id(st.pos), code(key)) != code(key):
             return NotImplemented
         first = not any(t is st.pos for t in written)
         dst.pos = mut(st.pos) if first else N.VmasMutVec()
@@ -117,6 +137,14 @@ def spawn_reset_where(scenario, mask, stages, writes, x_bounds, y_bounds, derive
             return NotImplemented  # (communication state: zeroed by World.reset, not by the launch)
         io.force[i], io.torque[i] = mut(a.state.__dict__.get("_force")), mut(a.state.__dict__.get("_torque"))
     keep = []
+    if sep is not None:
+        positions, desired = sep
+        order = _fused.reduce_order(dev, len(positions) - 1) if 2 <= len(positions) <= N.VMAS_RESET_MAX_SEP else None
+        if order is None:
+            return NotImplemented  # (no summation order reproduces torch's .mean(-1), or too long a list)
+        io.n_sep, io.sep_sum_mode, io.sep_desired = len(positions), order, float(desired)
+        for i, key in enumerate(positions):
+            io.sep_slot[i] = code(key)
     for i, d in enumerate(derived):
         r = io.derived[i]
         if d[0] == "norm":
@@ -134,6 +162,16 @@ def spawn_reset_where(scenario, mask, stages, writes, x_bounds, y_bounds, derive
             r.length, r.width, r.radius_lmd = rb.length, rb.width, rs.radius_lmd
             r.out8 = out.data_ptr()
             written.append(out)
+        elif d[0] == "mean_sq_sep":
+            _, index, factor, out = d
+            if sep is None or not isinstance(out, torch.Tensor) or out.shape != (B,):
+                return NotImplemented
+            r.kind, r.a, r.factor, r.out = N.VMAS_RESET_D_MEAN_SQ_SEP, int(index), float(factor), mut(out)
+        elif d[0] == "zero":
+            out = d[1]
+            if not isinstance(out, torch.Tensor) or out.shape != (B,):
+                return NotImplemented
+            r.kind, r.out = N.VMAS_RESET_D_ZERO32, mut(out)
         else:
             out = d[1]
             if not (isinstance(out, torch.Tensor) and out.dim() == 2 and _bool_rows(out, dev, (B, out.shape[1]))):
