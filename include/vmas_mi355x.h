@@ -54,8 +54,10 @@ extern "C" {
  * v13: VmasSamplingIO / vmas_sampling_outputs, VmasSamplingMaxPdfIO / vmas_sampling_max_pdf
  * v14: VmasResetDerived / VmasSpawnResetIO / vmas_spawn_reset
  * v15: VmasSpawnResetIO fixed-source writes (write_slot < 0), the separation list (n_sep / sep_*) and
- *      VMAS_RESET_D_MEAN_SQ_SEP / VMAS_RESET_D_ZERO32; VmasSamplingResetIO / vmas_sampling_reset */
-#define VMAS_ABI_VERSION 15
+ *      VMAS_RESET_D_MEAN_SQ_SEP / VMAS_RESET_D_ZERO32; VmasSamplingResetIO / vmas_sampling_reset
+ * v16: VmasWheelIO / vmas_wheel_outputs, VmasDispersionIO / vmas_dispersion_outputs,
+ *      VmasUniformResetIO / vmas_uniform_reset */
+#define VMAS_ABI_VERSION 16
 
 /* error codes */
 #define VMAS_OK 0
@@ -1413,6 +1415,114 @@ typedef struct VmasSamplingResetIO {
     float* sample[VMAS_SAMPLING_MAX_AGENTS]; /* [B] contiguous: agent.sample, in place */
 } VmasSamplingResetIO;
 int32_t vmas_sampling_reset(int32_t device, const VmasSamplingResetIO* io, uint64_t* increment, void* stream);
+
+/* ---- wheel (v16; reference vmas/scenarios/wheel.py `reward`, `observation`; restated in
+ * scenarios/wheel.py) ---------------------------------------------------------------------------------
+ * vmas_wheel_outputs: in one launch, one thread per env (a wave stages its 64 observation rows in LDS
+ * and stores them as one contiguous block per agent),
+ *   REWARD: rew[b] = | |line.ang_vel| - desired_velocity | ([B, 1], Scenario.rew) and rewards[i][b] =
+ *     -rew[b] for every agent;
+ *   OBS: per agent the 13 columns pos, vel, line.pos - pos, e1 - pos, -e1 - pos, remainder(line.rot,
+ *     pi) (torch.remainder: fmodf and the sign fix-up), |line.ang_vel|, rew recomputed, with e1 =
+ *     half_length * (cosf(line.rot), sinf(line.rot)) -- the library cos / sin, every operation fp32 and
+ *     rounded on its own.
+ * device -1: the host loop over the same statements (csrc/vmas_light_programs.hpp), libm's cosf / sinf. */
+#define VMAS_WHEEL_MAX_AGENTS 16
+typedef struct VmasWheelIO {
+    int32_t batch, n_agents, what, pad0;
+    float half_length;      /* f32(line_length / 2) */
+    float desired_velocity; /* f32 */
+    float pi;               /* f32(pi) */
+    float pad1;
+    VmasVec line_pos, line_rot, line_ang_vel; /* [B,2], [B,1], [B,1] */
+    VmasVec pos[VMAS_WHEEL_MAX_AGENTS];       /* [B,2] */
+    VmasVec vel[VMAS_WHEEL_MAX_AGENTS];       /* [B,2] */
+    float* rew;                               /* [B,1] fresh (REWARD) */
+    float* rewards[VMAS_WHEEL_MAX_AGENTS];    /* [B,1] fresh (REWARD) */
+    float* obs[VMAS_WHEEL_MAX_AGENTS];        /* [B,13] fresh (OBS) */
+    const int64_t* out_delta;                 /* optional: as VmasNavigationIO.out_delta */
+} VmasWheelIO;
+int32_t vmas_wheel_outputs(int32_t device, const VmasWheelIO* io, void* stream);
+
+/* ---- dispersion (v16; reference vmas/scenarios/dispersion.py `reward`, `observation`, `done`;
+ * restated in scenarios/dispersion.py) ---------------------------------------------------------------
+ * vmas_dispersion_outputs: in one launch, one thread per env -- the only writer of the env's flag
+ * rows -- with on(a, l) = |pos_a - pos_l| < thr[a][l] (strict; the norm as torch.linalg.vector_norm of a
+ * length-2 vector),
+ *   REWARD (the reward calls of every agent, in agent order): per food l how_many[l][b] = the agents on
+ *     it (int64), anyone[l][b] = how_many > 0, just_eaten |= anyone; agent a's reward = fp32 0 plus, in
+ *     food order, 1 for each food with just_eaten & ~eaten (share_reward) or 1 / how_many (the
+ *     correctly rounded fp32 reciprocal) for each food with on(a, l) & ~eaten; a reward that is exactly
+ *     0 becomes f32(-0.01) with penalise_by_time; then per food eaten |= just_eaten, just_eaten = 0,
+ *     is_rendering &= ~eaten (a NULL is_rendering row is skipped);
+ *   OBS: per agent pos, vel and per food (pos_l - pos, eaten as 0.0 / 1.0) -- with REWARD, the updated
+ *     eaten;
+ *   DONE: done[b] = every food eaten (the updated flags, with REWARD).
+ * A wave stages its 64 observation rows in LDS and stores them as one contiguous block per agent.  No
+ * atomics, no scratch.  device -1: the host loop over the same statements. */
+#define VMAS_DISP_MAX_AGENTS 16
+#define VMAS_DISP_MAX_FOOD 16
+typedef struct VmasDispersionIO {
+    int32_t batch, n_agents, n_food, what;
+    int32_t share_reward, penalise_by_time, pad0, pad1;
+    VmasVec pos[VMAS_DISP_MAX_AGENTS];     /* [B,2] */
+    VmasVec vel[VMAS_DISP_MAX_AGENTS];     /* [B,2] (OBS) */
+    VmasVec food_pos[VMAS_DISP_MAX_FOOD];  /* [B,2] */
+    float thr[VMAS_DISP_MAX_AGENTS * VMAS_DISP_MAX_FOOD]; /* [a * VMAS_DISP_MAX_FOOD + l] = f32(double(agent radius) + double(food radius)) */
+    uint8_t* eaten[VMAS_DISP_MAX_FOOD];        /* [B] torch.bool contiguous, in place (REWARD), read otherwise */
+    uint8_t* just_eaten[VMAS_DISP_MAX_FOOD];   /* [B] torch.bool contiguous, in place (REWARD) */
+    uint8_t* is_rendering[VMAS_DISP_MAX_FOOD]; /* [B] torch.bool contiguous, in place (REWARD), or NULL */
+    int64_t* how_many[VMAS_DISP_MAX_FOOD];     /* [B] fresh (REWARD) */
+    uint8_t* anyone[VMAS_DISP_MAX_FOOD];       /* [B] torch.bool fresh (REWARD) */
+    float* rewards[VMAS_DISP_MAX_AGENTS];      /* [B] fresh (REWARD) */
+    float* obs[VMAS_DISP_MAX_AGENTS];          /* [B, 4 + 3 * n_food] fresh (OBS) */
+    uint8_t* done;                             /* [B] torch.bool fresh (DONE) */
+    const int64_t* out_delta;                  /* optional: as VmasNavigationIO.out_delta */
+} VmasDispersionIO;
+int32_t vmas_dispersion_outputs(int32_t device, const VmasDispersionIO* io, void* stream);
+
+/* vmas_uniform_reset (v16) <- the reset of a scenario whose reset_world_at(None) is a fixed list of
+ * uniform_ calls that rejects nothing (wheel.py, dispersion.py `reset_world_at`), after World.reset, for
+ * the rows of a mask, in place, in ONE launch and with no host wait: one thread per env; a row outside
+ * the mask reads its mask byte only.  For a masked env b:
+ *   - draw record i is uniform_ call i of the full reset (call == i: every call is a record, in order).
+ *     VMAS_UDRAW_POS: a [B, 2] call over [lo, hi); the entity's pos = elements 2b and 2b + 1 of it.
+ *     VMAS_UDRAW_ROT: a [B, 1] call; the entity's pos = 0 and rot = element b.  The elements are those
+ *     of torch's uniform_ on a contiguous tensor of the call's own numel (2B or B: its own grid and
+ *     generator advance; mode as vmas_uniform_columns).  Every other state field of the entity is zeroed;
+ *   - fixed record j: the entity's pos = (x, y), every other state field zeroed;
+ *   - force[a] / torque[a] zeroed; clear[k][b] = 0 and set[k][b] = 1 (torch.bool rows); steps[b] = 0.
+ * *increment = what the full reset advances the generator by, known before the launch (the caller adds
+ * it).  A device path only (device -1: VMAS_E_INVALID). */
+#define VMAS_URESET_MAX_DRAWS 24
+#define VMAS_URESET_MAX_FIXED 16
+#define VMAS_URESET_MAX_AGENTS 16
+#define VMAS_URESET_MAX_CLEAR 32
+#define VMAS_URESET_MAX_SET 16
+#define VMAS_UDRAW_POS 0
+#define VMAS_UDRAW_ROT 1
+typedef struct VmasUniformDraw {
+    VmasResetEntity entity;
+    int32_t target, call; /* VMAS_UDRAW_*; the index of the uniform_ call within the full reset */
+    float lo, hi;         /* f32 bounds */
+} VmasUniformDraw;
+typedef struct VmasUniformFixed {
+    VmasResetEntity entity;
+    float x, y;
+} VmasUniformFixed;
+typedef struct VmasUniformResetIO {
+    int32_t batch, mode, n_draws, n_fixed;
+    int32_t n_agents, n_clear, n_set, pad0;
+    uint64_t seed, offset;
+    const uint8_t* mask; /* [B] torch.bool */
+    float* steps;        /* [B] contiguous, or NULL */
+    VmasUniformDraw draws[VMAS_URESET_MAX_DRAWS];
+    VmasUniformFixed fixed[VMAS_URESET_MAX_FIXED];
+    VmasMutVec force[VMAS_URESET_MAX_AGENTS], torque[VMAS_URESET_MAX_AGENTS];
+    uint8_t* clear[VMAS_URESET_MAX_CLEAR]; /* [B] torch.bool contiguous */
+    uint8_t* set[VMAS_URESET_MAX_SET];     /* [B] torch.bool contiguous */
+} VmasUniformResetIO;
+int32_t vmas_uniform_reset(int32_t device, const VmasUniformResetIO* io, uint64_t* increment, void* stream);
 
 #ifdef __cplusplus
 }

@@ -19,7 +19,7 @@ LIB_PATH = Path(os.environ.get("VMAS_LIB_PATH") or Path(__file__).resolve().pare
 
 # ------------------------------------------------------------------------------------------------
 # constants mirrored from include/vmas_mi355x.h
-VMAS_ABI_VERSION = 15
+VMAS_ABI_VERSION = 16
 VMAS_SPHERE, VMAS_BOX, VMAS_LINE = 0, 1, 2
 (
     VMAS_PAIR_JOINT,
@@ -87,6 +87,9 @@ EXPORTED_SYMBOLS = (
     "vmas_sampling_outputs",
     "vmas_sampling_max_pdf",
     "vmas_sampling_reset",
+    "vmas_wheel_outputs",
+    "vmas_dispersion_outputs",
+    "vmas_uniform_reset",
     "vmas_assert_publish_range",
     "vmas_transport_outputs",
     "vmas_discovery_outputs",
@@ -610,6 +613,65 @@ class VmasSamplingResetIO(ctypes.Structure):
     ]
 
 
+# wheel and dispersion (csrc/vmas_scenarios.hip k_wheel / k_dispersion; csrc/vmas_light_programs.hpp)
+VMAS_WHEEL_MAX_AGENTS = 16
+VMAS_DISP_MAX_AGENTS = 16
+VMAS_DISP_MAX_FOOD = 16
+_WA, _DA, _DF = VMAS_WHEEL_MAX_AGENTS, VMAS_DISP_MAX_AGENTS, VMAS_DISP_MAX_FOOD
+
+
+class VmasWheelIO(ctypes.Structure):
+    _fields_ = [
+        ("batch", _i32), ("n_agents", _i32), ("what", _i32), ("pad0", _i32),
+        ("half_length", _f32), ("desired_velocity", _f32), ("pi", _f32), ("pad1", _f32),
+        ("line_pos", VmasVec), ("line_rot", VmasVec), ("line_ang_vel", VmasVec),
+        ("pos", VmasVec * _WA), ("vel", VmasVec * _WA),
+        ("rew", _vp), ("rewards", _vp * _WA), ("obs", _vp * _WA),
+        ("out_delta", _vp),  # (graph mode's direct outputs: [obs, rewards, done] byte offsets)
+    ]
+
+
+class VmasDispersionIO(ctypes.Structure):
+    _fields_ = [
+        ("batch", _i32), ("n_agents", _i32), ("n_food", _i32), ("what", _i32),
+        ("share_reward", _i32), ("penalise_by_time", _i32), ("pad0", _i32), ("pad1", _i32),
+        ("pos", VmasVec * _DA), ("vel", VmasVec * _DA), ("food_pos", VmasVec * _DF),
+        ("thr", _f32 * (_DA * _DF)),
+        ("eaten", _vp * _DF), ("just_eaten", _vp * _DF), ("is_rendering", _vp * _DF),
+        ("how_many", _vp * _DF), ("anyone", _vp * _DF),
+        ("rewards", _vp * _DA), ("obs", _vp * _DA), ("done", _vp),
+        ("out_delta", _vp),  # (graph mode's direct outputs: [obs, rewards, done] byte offsets)
+    ]
+
+
+# the uniform reset (csrc/vmas_reset.hip k_uniform_reset; simulator/environment/_uniform_reset.py)
+VMAS_URESET_MAX_DRAWS = 24
+VMAS_URESET_MAX_FIXED = 16
+VMAS_URESET_MAX_AGENTS = 16
+VMAS_URESET_MAX_CLEAR = 32
+VMAS_URESET_MAX_SET = 16
+VMAS_UDRAW_POS, VMAS_UDRAW_ROT = 0, 1
+
+
+class VmasUniformDraw(ctypes.Structure):
+    _fields_ = [("entity", VmasResetEntity), ("target", _i32), ("call", _i32), ("lo", _f32), ("hi", _f32)]
+
+
+class VmasUniformFixed(ctypes.Structure):
+    _fields_ = [("entity", VmasResetEntity), ("x", _f32), ("y", _f32)]
+
+
+class VmasUniformResetIO(ctypes.Structure):
+    _fields_ = [
+        ("batch", _i32), ("mode", _i32), ("n_draws", _i32), ("n_fixed", _i32),
+        ("n_agents", _i32), ("n_clear", _i32), ("n_set", _i32), ("pad0", _i32),
+        ("seed", ctypes.c_uint64), ("offset", ctypes.c_uint64), ("mask", _vp), ("steps", _vp),
+        ("draws", VmasUniformDraw * VMAS_URESET_MAX_DRAWS), ("fixed", VmasUniformFixed * VMAS_URESET_MAX_FIXED),
+        ("force", VmasMutVec * VMAS_URESET_MAX_AGENTS), ("torque", VmasMutVec * VMAS_URESET_MAX_AGENTS),
+        ("clear", _vp * VMAS_URESET_MAX_CLEAR), ("set", _vp * VMAS_URESET_MAX_SET),
+    ]
+
+
 VMAS_TRANSPORT_MAX_PACKAGES = 8
 VMAS_TRANSPORT_MAX_AGENTS = 16
 _TP, _TA = VMAS_TRANSPORT_MAX_PACKAGES, VMAS_TRANSPORT_MAX_AGENTS
@@ -839,6 +901,12 @@ def load_library(path: os.PathLike | str | None = None) -> ctypes.CDLL:
     lib.vmas_sampling_max_pdf.argtypes = [_i32, _vp, _vp]
     lib.vmas_sampling_reset.restype = _i32
     lib.vmas_sampling_reset.argtypes = [_i32, _vp, ctypes.POINTER(ctypes.c_uint64), _vp]
+    lib.vmas_wheel_outputs.restype = _i32
+    lib.vmas_wheel_outputs.argtypes = [_i32, _vp, _vp]
+    lib.vmas_dispersion_outputs.restype = _i32
+    lib.vmas_dispersion_outputs.argtypes = [_i32, _vp, _vp]
+    lib.vmas_uniform_reset.restype = _i32
+    lib.vmas_uniform_reset.argtypes = [_i32, _vp, ctypes.POINTER(ctypes.c_uint64), _vp]
     lib.vmas_distance_vjp.restype = _i32
     lib.vmas_distance_vjp.argtypes = [_i32, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
     lib.vmas_cast_rays_vjp.restype = _i32

@@ -236,6 +236,50 @@ __global__ void __launch_bounds__(kResetThreads) k_reset_commit(VmasSpawnResetIO
     }
 }
 
+// ---- the uniform reset (vmas_uniform_reset) --------------------------------------------------------
+// A reset that is a fixed list of uniform_ calls and rejects nothing (wheel.py:49-78,
+// dispersion.py:51-88 `reset_world_at(None)`): one thread per env, as k_balance_reset.  Record i is call
+// i of the full reset, so the generator offset of a call is a running sum over the records before it:
+// a [B, 2] call advances by g2.inc (torch's grid on 2 B elements), a [B, 1] call by g1.inc.
+struct UniformGrids {
+    vmas_uniform::DrawGrid g2, g1;
+};
+static_assert(sizeof(VmasUniformResetIO) + sizeof(UniformGrids) <= 4096, "kernel argument block");
+
+__global__ void __launch_bounds__(kResetThreads) k_uniform_reset(VmasUniformResetIO io_arg, UniformGrids g) {
+    VMAS_PROGRAM_ARGS(VmasUniformResetIO, io_arg);
+    const int b = blockIdx.x * kResetThreads + threadIdx.x;
+    if (b >= io.batch || io.mask[b] == 0) return;
+    unsigned long long off = io.offset;
+    for (int i = 0; i < io.n_draws; ++i) {
+        const VmasResetEntity e = io.draws[i].entity;
+        const float lo = io.draws[i].lo, hi = io.draws[i].hi;
+        if (io.draws[i].target == VMAS_UDRAW_POS) {
+            const float x = vmas_uniform::uniform_at(io.seed, off, g.g2, 2 * b, lo, hi, io.mode);
+            const float y = vmas_uniform::uniform_at(io.seed, off, g.g2, 2 * b + 1, lo, hi, io.mode);
+            reset_place(e, b, mk(x, y));
+            off += g.g2.inc;
+        } else {
+            const float r = vmas_uniform::uniform_at(io.seed, off, g.g1, b, lo, hi, io.mode);
+            reset_place(e, b, mk(0.f, 0.f));
+            put1(e.rot, b, r);
+            off += g.g1.inc;
+        }
+    }
+    for (int i = 0; i < io.n_fixed; ++i) {
+        const VmasResetEntity e = io.fixed[i].entity;
+        reset_place(e, b, mk(io.fixed[i].x, io.fixed[i].y));
+    }
+    for (int a = 0; a < io.n_agents; ++a) {
+        const VmasMutVec f = io.force[a], t = io.torque[a];
+        put2(f, b, 0.f, 0.f);
+        put1(t, b, 0.f);
+    }
+    for (int k = 0; k < io.n_clear; ++k) io.clear[k][b] = 0;
+    for (int k = 0; k < io.n_set; ++k) io.set[k][b] = 1;
+    if (io.steps) io.steps[b] = 0.f;
+}
+
 std::mutex g_reset_mu;
 int32_t* g_reset_host_words[64] = {nullptr};  // pinned: the words of the last call, per device
 
@@ -348,5 +392,54 @@ extern "C" int32_t vmas_spawn_reset(int32_t device, const VmasSpawnResetIO* io, 
     for (int i = 0; i < io->n_place; ++i) tries += (unsigned long long)(h[i] == 0 ? 1 : h[i] + 2);
     *increment = tries * 2ull * inc;
     *unresolved = h[VMAS_RESET_MAX_PLACE];
+    return VMAS_OK;
+}
+
+extern "C" int32_t vmas_uniform_reset(int32_t device, const VmasUniformResetIO* io, uint64_t* increment, void* stream) {
+    if (!io || !increment) return vmas_aux::fail(VMAS_E_INVALID, "vmas_uniform_reset: null argument block");
+    if (device < 0 || device >= 64)
+        return vmas_aux::fail(VMAS_E_INVALID, "vmas_uniform_reset: device %d (the draws are a device path only)", device);
+    // (element 2 b + 1 of a [B, 2] call is an int)
+    if (io->batch <= 0 || io->batch > (1 << 30) - 1 || io->mode < 0 || io->mode > 3 || io->n_draws < 0 ||
+        io->n_draws > VMAS_URESET_MAX_DRAWS || io->n_fixed < 0 || io->n_fixed > VMAS_URESET_MAX_FIXED || io->n_agents < 0 ||
+        io->n_agents > VMAS_URESET_MAX_AGENTS || io->n_clear < 0 || io->n_clear > VMAS_URESET_MAX_CLEAR || io->n_set < 0 ||
+        io->n_set > VMAS_URESET_MAX_SET || !io->mask)
+        return vmas_aux::fail(VMAS_E_INVALID, "vmas_uniform_reset: bad arguments (batch %d, %d draws, %d fixed)", io->batch,
+                              io->n_draws, io->n_fixed);
+    int n2 = 0, n1 = 0;
+    for (int i = 0; i < io->n_draws; ++i) {
+        const VmasUniformDraw& d = io->draws[i];
+        if (d.call != i || (d.target != VMAS_UDRAW_POS && d.target != VMAS_UDRAW_ROT))
+            return vmas_aux::fail(VMAS_E_INVALID, "vmas_uniform_reset: draw record %d (call %d, target %d)", i, d.call,
+                                  d.target);
+        if (d.target == VMAS_UDRAW_POS ? !d.entity.pos.p : !d.entity.rot.p)
+            return vmas_aux::fail(VMAS_E_INVALID, "vmas_uniform_reset: null destination (draw record %d)", i);
+        (d.target == VMAS_UDRAW_POS ? n2 : n1) += 1;
+    }
+    for (int i = 0; i < io->n_fixed; ++i)
+        if (!io->fixed[i].entity.pos.p)
+            return vmas_aux::fail(VMAS_E_INVALID, "vmas_uniform_reset: null destination (fixed record %d)", i);
+    for (int k = 0; k < io->n_clear; ++k)
+        if (!io->clear[k]) return vmas_aux::fail(VMAS_E_INVALID, "vmas_uniform_reset: null row to clear (%d)", k);
+    for (int k = 0; k < io->n_set; ++k)
+        if (!io->set[k]) return vmas_aux::fail(VMAS_E_INVALID, "vmas_uniform_reset: null row to set (%d)", k);
+    VMAS_AUX_HIP(hipSetDevice(device));
+    static int max_blocks[64] = {0};
+    if (!max_blocks[device]) {
+        hipDeviceProp_t prop;
+        VMAS_AUX_HIP(hipGetDeviceProperties(&prop, device));
+        max_blocks[device] = prop.multiProcessorCount * (prop.maxThreadsPerMultiProcessor / vmas_uniform::kThreads);
+        if (max_blocks[device] <= 0) return vmas_aux::fail(VMAS_E_HIP, "vmas_uniform_reset: device properties");
+    }
+    // torch's distribution-kernel grid and per-call philox increment: on 2 B elements and on B elements
+    int gx2 = 0, gx1 = 0;
+    unsigned long long inc2 = 0, inc1 = 0;
+    vmas_uniform::grid_for(2ll * io->batch, max_blocks[device], &gx2, &inc2);
+    vmas_uniform::grid_for(io->batch, max_blocks[device], &gx1, &inc1);
+    const UniformGrids g{{(long long)vmas_uniform::kThreads * gx2, inc2}, {(long long)vmas_uniform::kThreads * gx1, inc1}};
+    const int gx = (io->batch + kResetThreads - 1) / kResetThreads;
+    hipLaunchKernelGGL(k_uniform_reset, dim3(gx), dim3(kResetThreads), 0, (hipStream_t)stream, *io, g);
+    VMAS_AUX_HIP(hipGetLastError());
+    *increment = inc2 * (unsigned long long)n2 + inc1 * (unsigned long long)n1;
     return VMAS_OK;
 }

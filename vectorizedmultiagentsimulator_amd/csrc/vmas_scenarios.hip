@@ -13,6 +13,7 @@
 
 #include "vmas_aux.hpp"
 #include "vmas_lidar.hpp"
+#include "vmas_light_programs.hpp"
 #include "vmas_mi355x.h"
 #include "vmas_programs.hpp"
 #include "vmas_query.hpp"
@@ -1284,6 +1285,63 @@ const char* samp_density_error(const VmasSamplingGrid& g, const VmasSamplingDens
     return nullptr;
 }
 
+// ---- wheel and dispersion (vmas_light_programs.hpp has the row functions) ------------------------------
+// Both programs move a few hundred bytes per env and are launch-latency-bound at every measured size,
+// so the mapping is the plainest one that stores coalesced: a thread per env, a wave per 64 envs; per
+// agent the wave stages its 64 observation rows in LDS (4 x 64 x W floats, sized by the launch) and
+// stores them as ONE contiguous block (a lane storing its own row writes 4-byte values 4 W bytes
+// apart).  One thread computes everything of its env, so the dispersion flags have one writer and no
+// other thread reads them: no atomics, no ordering between threads.
+__global__ void __launch_bounds__(256) k_wheel(VmasWheelIO io_arg) {
+    VMAS_PROGRAM_ARGS(VmasWheelIO, io_arg);
+    extern __shared__ float light_lds[];
+    constexpr int W = 13;
+    const int lane = (int)(threadIdx.x & 63u), w = (int)(threadIdx.x >> 6);
+    const int g0 = wave_uniform(((int)blockIdx.x * 4 + w) * 64), b = g0 + lane;
+    if (g0 >= io.batch) return;  // (wave-uniform; no workgroup barrier below)
+    const bool valid = b < io.batch;
+    const OutDelta od = load_out_delta(io);
+    if (valid && (io.what & VMAS_SCN_REWARD)) {
+        const float r = vmas_light::wheel_rew(io, (long)b);
+        io.rew[b] = r;
+        for (int k = 0; k < io.n_agents; ++k) moved(io.rewards[k], od.rew)[b] = -r;
+    }
+    if (!(io.what & VMAS_SCN_OBS)) return;
+    float* S = light_lds + w * 64 * W;
+    const int nv = io.batch - g0 < 64 ? io.batch - g0 : 64;
+    for (int k = 0; k < io.n_agents; ++k) {
+        if (valid) vmas_light::wheel_obs_row(io, (long)b, k, S + lane * W);
+        __builtin_amdgcn_wave_barrier();
+        rows_out(S, nv, W, moved(io.obs[k], od.obs) + (long)g0 * W, lane, 64, nullptr, (float*)nullptr, 0, 0, lane);
+        __builtin_amdgcn_wave_barrier();
+    }
+}
+
+__global__ void __launch_bounds__(256) k_dispersion(VmasDispersionIO io_arg) {
+    VMAS_PROGRAM_ARGS(VmasDispersionIO, io_arg);
+    extern __shared__ float light_lds[];
+    const int lane = (int)(threadIdx.x & 63u), w = (int)(threadIdx.x >> 6);
+    const int g0 = wave_uniform(((int)blockIdx.x * 4 + w) * 64), b = g0 + lane;
+    if (g0 >= io.batch) return;  // (wave-uniform; no workgroup barrier below)
+    const bool valid = b < io.batch;
+    const OutDelta od = load_out_delta(io);
+    vmas_light::DispFlags f{0u};
+    if (valid) {
+        f = (io.what & VMAS_SCN_REWARD) ? vmas_light::disp_reward(io, (long)b, od.rew) : vmas_light::disp_load_flags(io, (long)b);
+        if (io.what & VMAS_SCN_DONE) moved(io.done, od.done)[b] = vmas_light::disp_done(io, f) ? 1 : 0;
+    }
+    if (!(io.what & VMAS_SCN_OBS)) return;
+    const int W = 4 + 3 * io.n_food;
+    float* S = light_lds + w * 64 * W;
+    const int nv = io.batch - g0 < 64 ? io.batch - g0 : 64;
+    for (int k = 0; k < io.n_agents; ++k) {
+        if (valid) vmas_light::disp_obs_row(io, (long)b, k, f, S + lane * W);
+        __builtin_amdgcn_wave_barrier();
+        rows_out(S, nv, W, moved(io.obs[k], od.obs) + (long)g0 * W, lane, 64, nullptr, (float*)nullptr, 0, 0, lane);
+        __builtin_amdgcn_wave_barrier();
+    }
+}
+
 // Test kernel (tests/test_fused.py test_exact_math_gpu): the flag-independent division / square
 // root of vmas_programs.hpp next to this translation unit's IEEE `/` and sqrtf.
 __global__ void k_test_exact_math(const float* a, const float* b, float* out, long n) {
@@ -1513,6 +1571,75 @@ int32_t vmas_sampling_reset(int32_t device, const VmasSamplingResetIO* io, uint6
     hipLaunchKernelGGL(k_sampling_reset, dim3((io->batch + 3) / 4), dim3(256), 0, (hipStream_t)stream, *io, g);
     VMAS_AUX_HIP(hipGetLastError());
     *increment = inc * 2ull * (unsigned long long)(io->density.n_gaussians + io->n_agents);
+    return VMAS_OK;
+}
+
+int32_t vmas_wheel_outputs(int32_t device, const VmasWheelIO* io, void* stream) {
+    static_assert(sizeof(VmasWheelIO) <= 4096, "kernel argument block");
+    if (!io || device >= 64 || io->batch <= 0 || io->n_agents < 1 || io->n_agents > VMAS_WHEEL_MAX_AGENTS ||
+        !(io->what & (VMAS_SCN_REWARD | VMAS_SCN_OBS)) || !io->line_ang_vel.p)
+        return vmas_aux::fail(VMAS_E_INVALID, "vmas_wheel_outputs: bad arguments");
+    const bool rew = (io->what & VMAS_SCN_REWARD) != 0, obs = (io->what & VMAS_SCN_OBS) != 0;
+    if ((rew && !io->rew) || (obs && (!io->line_pos.p || !io->line_rot.p)))
+        return vmas_aux::fail(VMAS_E_INVALID, "vmas_wheel_outputs: null pointer");
+    const int n = io->n_agents;
+    for (int i = 0; i < n; ++i)
+        if ((rew && !io->rewards[i]) || (obs && (!io->pos[i].p || !io->vel[i].p || !io->obs[i])))
+            return vmas_aux::fail(VMAS_E_INVALID, "vmas_wheel_outputs: null pointer (agent %d)", i);
+    constexpr int W = 13;
+    if (device < 0) {
+        if (io->out_delta) return vmas_aux::fail(VMAS_E_INVALID, "vmas_wheel_outputs: out_delta on the host");
+        for (long b = 0; b < io->batch; ++b) {
+            if (rew) {
+                const float r = vmas_light::wheel_rew(*io, b);
+                io->rew[b] = r;
+                for (int k = 0; k < n; ++k) io->rewards[k][b] = -r;
+            }
+            if (obs)
+                for (int k = 0; k < n; ++k) vmas_light::wheel_obs_row(*io, b, k, io->obs[k] + b * W);
+        }
+        return VMAS_OK;
+    }
+    VMAS_AUX_HIP(hipSetDevice(device));
+    hipLaunchKernelGGL(k_wheel, dim3((io->batch + 255) / 256), dim3(256), (size_t)4 * 64 * W * sizeof(float),
+                       (hipStream_t)stream, *io);
+    VMAS_AUX_HIP(hipGetLastError());
+    return VMAS_OK;
+}
+
+int32_t vmas_dispersion_outputs(int32_t device, const VmasDispersionIO* io, void* stream) {
+    static_assert(sizeof(VmasDispersionIO) <= 4096, "kernel argument block");
+    static_assert(VMAS_DISP_MAX_AGENTS <= 32 && VMAS_DISP_MAX_FOOD <= 32, "a bit per agent / per food");
+    if (!io || device >= 64 || io->batch <= 0 || io->n_agents < 1 || io->n_agents > VMAS_DISP_MAX_AGENTS ||
+        io->n_food < 1 || io->n_food > VMAS_DISP_MAX_FOOD ||
+        !(io->what & (VMAS_SCN_REWARD | VMAS_SCN_OBS | VMAS_SCN_DONE)))
+        return vmas_aux::fail(VMAS_E_INVALID, "vmas_dispersion_outputs: bad arguments");
+    const bool rew = (io->what & VMAS_SCN_REWARD) != 0, obs = (io->what & VMAS_SCN_OBS) != 0;
+    const bool done = (io->what & VMAS_SCN_DONE) != 0;
+    const int n = io->n_agents, nf = io->n_food;
+    if (done && !io->done) return vmas_aux::fail(VMAS_E_INVALID, "vmas_dispersion_outputs: null pointer (done)");
+    for (int l = 0; l < nf; ++l)
+        if (!io->eaten[l] || ((rew || obs) && !io->food_pos[l].p) ||
+            (rew && (!io->just_eaten[l] || !io->how_many[l] || !io->anyone[l])))
+            return vmas_aux::fail(VMAS_E_INVALID, "vmas_dispersion_outputs: null pointer (food %d)", l);
+    for (int i = 0; i < n; ++i)
+        if (((rew || obs) && !io->pos[i].p) || (rew && !io->rewards[i]) || (obs && (!io->vel[i].p || !io->obs[i])))
+            return vmas_aux::fail(VMAS_E_INVALID, "vmas_dispersion_outputs: null pointer (agent %d)", i);
+    const int W = 4 + 3 * nf;
+    if (device < 0) {
+        if (io->out_delta) return vmas_aux::fail(VMAS_E_INVALID, "vmas_dispersion_outputs: out_delta on the host");
+        for (long b = 0; b < io->batch; ++b) {
+            const vmas_light::DispFlags f = rew ? vmas_light::disp_reward(*io, b, 0) : vmas_light::disp_load_flags(*io, b);
+            if (done) io->done[b] = vmas_light::disp_done(*io, f) ? 1 : 0;
+            if (obs)
+                for (int k = 0; k < n; ++k) vmas_light::disp_obs_row(*io, b, k, f, io->obs[k] + b * W);
+        }
+        return VMAS_OK;
+    }
+    VMAS_AUX_HIP(hipSetDevice(device));
+    hipLaunchKernelGGL(k_dispersion, dim3((io->batch + 255) / 256), dim3(256), (size_t)4 * 64 * W * sizeof(float),
+                       (hipStream_t)stream, *io);
+    VMAS_AUX_HIP(hipGetLastError());
     return VMAS_OK;
 }
 

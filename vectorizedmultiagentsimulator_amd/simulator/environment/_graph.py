@@ -136,7 +136,8 @@ _STEP_METHODS = ("reward", "observation", "done", "info", "pre_step", "post_step
 # tests/test_graph.py, navigation, held to it by tests/test_navigation_gpu.py, and sampling, held to
 # it by tests/test_sampling_gpu.py (not
 # every file of the scenarios directory -- the debug scenarios are replayed like a user's scenario).
-_TRUSTED_FILES = ("balance.py", "transport.py", "discovery.py", "flocking.py", "navigation.py", "sampling.py")
+_TRUSTED_FILES = ("balance.py", "transport.py", "discovery.py", "flocking.py", "navigation.py", "sampling.py",
+                  "wheel.py", "dispersion.py")
 
 
 def _trusted_scenario(scenario) -> bool:
