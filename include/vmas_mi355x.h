@@ -56,8 +56,9 @@ extern "C" {
  * v15: VmasSpawnResetIO fixed-source writes (write_slot < 0), the separation list (n_sep / sep_*) and
  *      VMAS_RESET_D_MEAN_SQ_SEP / VMAS_RESET_D_ZERO32; VmasSamplingResetIO / vmas_sampling_reset
  * v16: VmasWheelIO / vmas_wheel_outputs, VmasDispersionIO / vmas_dispersion_outputs,
- *      VmasUniformResetIO / vmas_uniform_reset */
-#define VMAS_ABI_VERSION 16
+ *      VmasUniformResetIO / vmas_uniform_reset
+ * v17: VmasMpeIO / vmas_mpe_outputs */
+#define VMAS_ABI_VERSION 17
 
 /* error codes */
 #define VMAS_OK 0
@@ -1523,6 +1524,73 @@ typedef struct VmasUniformResetIO {
     uint8_t* set[VMAS_URESET_MAX_SET];     /* [B] torch.bool contiguous */
 } VmasUniformResetIO;
 int32_t vmas_uniform_reset(int32_t device, const VmasUniformResetIO* io, uint64_t* increment, void* stream);
+
+/* ---- the MPE family (v17; reference vmas/scenarios/mpe/simple_spread.py, simple_tag.py `reward`,
+ * `observation`; restated in scenarios/mpe/) -------------------------------------------------------------
+ * vmas_mpe_outputs: in one launch, one thread per env (a wave stages its 64 observation rows in LDS and
+ * stores them as one contiguous block per agent), with |.| the norm as torch.linalg.vector_norm of a
+ * length-2 vector (sqrtf(dx * dx + dy * dy), correctly rounded), every operation fp32 and rounded on its
+ * own, no atomics, no scratch.
+ *   REWARD, task VMAS_MPE_SPREAD (the first agent's reward call): closest[l] = the minimum over the
+ *     agents, in order, of |a.pos - l.pos| (torch.min: a NaN wins); r = 0; for each agent i in order: for
+ *     each landmark l in order r = r - closest[l]; then, when bit i of collide_mask is set, for each other
+ *     agent a in order r = r - 1 where (|a.pos - i.pos| - radius[a]) - radius[i] < 0 (World.is_overlapping
+ *     of two spheres).  rew[b] = r (Scenario.rew) and rewards[i][b] = r for every agent.
+ *   REWARD, task VMAS_MPE_TAG: bit i of adversary_mask: agent i is an adversary; hit(i, j) = |i.pos -
+ *     j.pos| < thr[i * VMAS_MPE_MAX_AGENTS + j] (strict; thr = f32(double(r_i) + double(r_j))).  A good agent
+ *     i: r = 0; with shape_agent_rew, for each adversary a in order r = r + f32(0.1) * |i.pos - a.pos|; with
+ *     its collide bit, for each adversary a in order r = r - 10 where hit(a, i).  An adversary i: r = 0;
+ *     with shape_adversary_rew r = r - f32(0.1) * (the minimum over the good agents g, in order, of |g.pos -
+ *     i.pos|); with its collide bit, for each good agent g in order r = r + 10 where hit(g, i).
+ *     agent_rew[i][b] = r (Agent.rew).  agents_rew[b] / adverary_rew[b] = the sum of the good agents' / the
+ *     adversaries' r in the order of torch's .sum(-1) over a contiguous [B, n] tensor: sum_mode_good /
+ *     sum_mode_adv strided accumulators (element k of the team goes to accumulator k % count), combined by an
+ *     adjacent-pair tree -- the count the host probed for this device and n (simulator/_fused.py
+ *     reduce_order; both teams have at least one member).  rewards[i][b] = the team's sum with its share
+ *     flag, else r.
+ *   OBS: agent k's row is its n_terms[k] terms in table order, two columns each: VMAS_MPE_SELF_VEL vel[k];
+ *     VMAS_MPE_SELF_POS pos[k]; VMAS_MPE_REL_LANDMARK landmark_pos[index] - pos[k]; VMAS_MPE_REL_AGENT
+ *     pos[index] - pos[k]; VMAS_MPE_AGENT_VEL vel[index].  The row is 2 * n_terms[k] floats wide.
+ * device -1: the host loop over the same statements (csrc/vmas_mpe_programs.hpp). */
+#define VMAS_MPE_MAX_AGENTS 8
+#define VMAS_MPE_MAX_LANDMARKS 8
+#define VMAS_MPE_MAX_TERMS 24 /* 2 own + 8 landmarks + 7 other positions + 7 other velocities */
+#define VMAS_MPE_SPREAD 1
+#define VMAS_MPE_TAG 2
+#define VMAS_MPE_SELF_VEL 0
+#define VMAS_MPE_SELF_POS 1
+#define VMAS_MPE_REL_LANDMARK 2
+#define VMAS_MPE_REL_AGENT 3
+#define VMAS_MPE_AGENT_VEL 4
+typedef struct VmasMpeTerm {
+    uint8_t kind, index; /* VMAS_MPE_*; the landmark / agent a relative or foreign term reads */
+} VmasMpeTerm;
+typedef struct VmasMpeIO {
+    int32_t batch, n_agents, n_landmarks, what;
+    int32_t task;          /* VMAS_MPE_SPREAD | VMAS_MPE_TAG */
+    uint32_t collide_mask; /* bit i: agent i's `collide` */
+    const int64_t* out_delta; /* optional: as VmasNavigationIO.out_delta */
+    VmasVec pos[VMAS_MPE_MAX_AGENTS];              /* [B,2] */
+    VmasVec vel[VMAS_MPE_MAX_AGENTS];              /* [B,2] (OBS) */
+    VmasVec landmark_pos[VMAS_MPE_MAX_LANDMARKS];  /* [B,2] */
+    int32_t n_terms[VMAS_MPE_MAX_AGENTS];          /* agent k's row: 2 * n_terms[k] columns */
+    VmasMpeTerm terms[VMAS_MPE_MAX_AGENTS][VMAS_MPE_MAX_TERMS];
+    /* spread */
+    float radius[VMAS_MPE_MAX_AGENTS]; /* f32 sphere radii (is_overlapping subtracts them one by one) */
+    /* tag */
+    uint32_t adversary_mask;
+    int32_t shape_agent_rew, shape_adversary_rew, agents_share_rew, adversaries_share_rew;
+    int32_t sum_mode_good, sum_mode_adv, pad0; /* accumulator counts of the team sums (1, 2, 4 or 8) */
+    float thr[VMAS_MPE_MAX_AGENTS * VMAS_MPE_MAX_AGENTS]; /* [i * VMAS_MPE_MAX_AGENTS + j] = f32(double(r_i) + double(r_j)) */
+    /* outputs */
+    float* rewards[VMAS_MPE_MAX_AGENTS];   /* [B] fresh per agent: what reward(agent) returns (REWARD) */
+    float* rew;                            /* spread: [B] fresh, Scenario.rew (REWARD) */
+    float* agent_rew[VMAS_MPE_MAX_AGENTS]; /* tag: [B] fresh, Agent.rew (REWARD) */
+    float* agents_rew;                     /* tag: [B] fresh, Scenario.agents_rew (REWARD) */
+    float* adverary_rew;                   /* tag: [B] fresh, Scenario.adverary_rew (REWARD; the reference's spelling) */
+    float* obs[VMAS_MPE_MAX_AGENTS];       /* [B, 2 * n_terms[k]] fresh (OBS) */
+} VmasMpeIO;
+int32_t vmas_mpe_outputs(int32_t device, const VmasMpeIO* io, void* stream);
 
 #ifdef __cplusplus
 }

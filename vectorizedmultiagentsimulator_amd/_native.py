@@ -19,7 +19,7 @@ LIB_PATH = Path(os.environ.get("VMAS_LIB_PATH") or Path(__file__).resolve().pare
 
 # ------------------------------------------------------------------------------------------------
 # constants mirrored from include/vmas_mi355x.h
-VMAS_ABI_VERSION = 16
+VMAS_ABI_VERSION = 17
 VMAS_SPHERE, VMAS_BOX, VMAS_LINE = 0, 1, 2
 (
     VMAS_PAIR_JOINT,
@@ -90,6 +90,7 @@ EXPORTED_SYMBOLS = (
     "vmas_wheel_outputs",
     "vmas_dispersion_outputs",
     "vmas_uniform_reset",
+    "vmas_mpe_outputs",
     "vmas_assert_publish_range",
     "vmas_transport_outputs",
     "vmas_discovery_outputs",
@@ -644,6 +645,36 @@ class VmasDispersionIO(ctypes.Structure):
     ]
 
 
+# the MPE family (csrc/vmas_scenarios.hip k_mpe; csrc/vmas_mpe_programs.hpp)
+VMAS_MPE_MAX_AGENTS = 8
+VMAS_MPE_MAX_LANDMARKS = 8
+VMAS_MPE_MAX_TERMS = 24
+VMAS_MPE_SPREAD, VMAS_MPE_TAG = 1, 2
+VMAS_MPE_SELF_VEL, VMAS_MPE_SELF_POS, VMAS_MPE_REL_LANDMARK, VMAS_MPE_REL_AGENT, VMAS_MPE_AGENT_VEL = 0, 1, 2, 3, 4
+_MA, _ML = VMAS_MPE_MAX_AGENTS, VMAS_MPE_MAX_LANDMARKS
+
+
+class VmasMpeTerm(ctypes.Structure):
+    _fields_ = [("kind", ctypes.c_uint8), ("index", ctypes.c_uint8)]
+
+
+class VmasMpeIO(ctypes.Structure):
+    _fields_ = [
+        ("batch", _i32), ("n_agents", _i32), ("n_landmarks", _i32), ("what", _i32),
+        ("task", _i32), ("collide_mask", ctypes.c_uint32),
+        ("out_delta", _vp),  # (graph mode's direct outputs: [obs, rewards, done] byte offsets)
+        ("pos", VmasVec * _MA), ("vel", VmasVec * _MA), ("landmark_pos", VmasVec * _ML),
+        ("n_terms", _i32 * _MA), ("terms", (VmasMpeTerm * VMAS_MPE_MAX_TERMS) * _MA),
+        ("radius", _f32 * _MA),
+        ("adversary_mask", ctypes.c_uint32),
+        ("shape_agent_rew", _i32), ("shape_adversary_rew", _i32), ("agents_share_rew", _i32),
+        ("adversaries_share_rew", _i32), ("sum_mode_good", _i32), ("sum_mode_adv", _i32), ("pad0", _i32),
+        ("thr", _f32 * (_MA * _MA)),
+        ("rewards", _vp * _MA), ("rew", _vp), ("agent_rew", _vp * _MA), ("agents_rew", _vp), ("adverary_rew", _vp),
+        ("obs", _vp * _MA),
+    ]
+
+
 # the uniform reset (csrc/vmas_reset.hip k_uniform_reset; simulator/environment/_uniform_reset.py)
 VMAS_URESET_MAX_DRAWS = 24
 VMAS_URESET_MAX_FIXED = 16
@@ -905,6 +936,8 @@ def load_library(path: os.PathLike | str | None = None) -> ctypes.CDLL:
     lib.vmas_wheel_outputs.argtypes = [_i32, _vp, _vp]
     lib.vmas_dispersion_outputs.restype = _i32
     lib.vmas_dispersion_outputs.argtypes = [_i32, _vp, _vp]
+    lib.vmas_mpe_outputs.restype = _i32
+    lib.vmas_mpe_outputs.argtypes = [_i32, _vp, _vp]
     lib.vmas_uniform_reset.restype = _i32
     lib.vmas_uniform_reset.argtypes = [_i32, _vp, ctypes.POINTER(ctypes.c_uint64), _vp]
     lib.vmas_distance_vjp.restype = _i32

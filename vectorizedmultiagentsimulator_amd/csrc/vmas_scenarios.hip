@@ -15,6 +15,7 @@
 #include "vmas_lidar.hpp"
 #include "vmas_light_programs.hpp"
 #include "vmas_mi355x.h"
+#include "vmas_mpe_programs.hpp"
 #include "vmas_programs.hpp"
 #include "vmas_query.hpp"
 #include "vmas_uniform.hpp"
@@ -1342,6 +1343,37 @@ __global__ void __launch_bounds__(256) k_dispersion(VmasDispersionIO io_arg) {
     }
 }
 
+// ---- the MPE family (vmas_mpe_programs.hpp has the row functions) -----------------------------------------
+// The k_wheel form: a thread per env computes the task's reward block, then per agent the wave stages its
+// 64 observation rows in LDS (4 x 64 x the widest row, sized by the launch) and stores them as one
+// contiguous block.  The rows' widths differ per agent (the term table), so the LDS rows are re-laid per
+// agent.  A few hundred bytes per env: launch-latency-bound like its two neighbours.
+__global__ void __launch_bounds__(256) k_mpe(VmasMpeIO io_arg, int w_max) {
+    VMAS_PROGRAM_ARGS(VmasMpeIO, io_arg);
+    extern __shared__ float light_lds[];
+    const int lane = (int)(threadIdx.x & 63u), w = (int)(threadIdx.x >> 6);
+    const int g0 = wave_uniform(((int)blockIdx.x * 4 + w) * 64), b = g0 + lane;
+    if (g0 >= io.batch) return;  // (wave-uniform; no workgroup barrier below)
+    const bool valid = b < io.batch;
+    const OutDelta od = load_out_delta(io);
+    if (valid && (io.what & VMAS_SCN_REWARD)) {
+        if (io.task == VMAS_MPE_SPREAD)
+            vmas_mpe::spread_reward(io, (long)b, od.rew);
+        else
+            vmas_mpe::tag_reward(io, (long)b, od.rew);
+    }
+    if (!(io.what & VMAS_SCN_OBS)) return;
+    float* S = light_lds + w * 64 * w_max;
+    const int nv = io.batch - g0 < 64 ? io.batch - g0 : 64;
+    for (int k = 0; k < io.n_agents; ++k) {
+        const int W = 2 * io.n_terms[k];
+        if (valid) vmas_mpe::obs_row(io, (long)b, k, S + lane * W);
+        __builtin_amdgcn_wave_barrier();
+        rows_out(S, nv, W, moved(io.obs[k], od.obs) + (long)g0 * W, lane, 64, nullptr, (float*)nullptr, 0, 0, lane);
+        __builtin_amdgcn_wave_barrier();
+    }
+}
+
 // Test kernel (tests/test_fused.py test_exact_math_gpu): the flag-independent division / square
 // root of vmas_programs.hpp next to this translation unit's IEEE `/` and sqrtf.
 __global__ void k_test_exact_math(const float* a, const float* b, float* out, long n) {
@@ -1639,6 +1671,68 @@ int32_t vmas_dispersion_outputs(int32_t device, const VmasDispersionIO* io, void
     VMAS_AUX_HIP(hipSetDevice(device));
     hipLaunchKernelGGL(k_dispersion, dim3((io->batch + 255) / 256), dim3(256), (size_t)4 * 64 * W * sizeof(float),
                        (hipStream_t)stream, *io);
+    VMAS_AUX_HIP(hipGetLastError());
+    return VMAS_OK;
+}
+
+int32_t vmas_mpe_outputs(int32_t device, const VmasMpeIO* io, void* stream) {
+    static_assert(sizeof(VmasMpeIO) + sizeof(int) <= 4096, "kernel argument block");
+    static_assert(VMAS_MPE_MAX_AGENTS <= 8, "a bit per agent; the registers of team_sum's tree");
+    if (!io || device >= 64 || io->batch <= 0 || io->n_agents < 1 || io->n_agents > VMAS_MPE_MAX_AGENTS ||
+        io->n_landmarks < 0 || io->n_landmarks > VMAS_MPE_MAX_LANDMARKS || !(io->what & (VMAS_SCN_REWARD | VMAS_SCN_OBS)) ||
+        (io->what & ~(VMAS_SCN_REWARD | VMAS_SCN_OBS)))
+        return vmas_aux::fail(VMAS_E_INVALID, "vmas_mpe_outputs: bad arguments");
+    if (io->task != VMAS_MPE_SPREAD && io->task != VMAS_MPE_TAG)
+        return vmas_aux::fail(VMAS_E_INVALID, "vmas_mpe_outputs: unknown task %d", io->task);
+    const bool rew = (io->what & VMAS_SCN_REWARD) != 0, obs = (io->what & VMAS_SCN_OBS) != 0;
+    const int n = io->n_agents, nl = io->n_landmarks;
+    const uint32_t all = (1u << n) - 1u;
+    if (rew && io->task == VMAS_MPE_SPREAD && !io->rew) return vmas_aux::fail(VMAS_E_INVALID, "vmas_mpe_outputs: null pointer (rew)");
+    if (rew && io->task == VMAS_MPE_TAG) {
+        if (!io->agents_rew || !io->adverary_rew)
+            return vmas_aux::fail(VMAS_E_INVALID, "vmas_mpe_outputs: null pointer (team sums)");
+        if (!(io->adversary_mask & all) || !(~io->adversary_mask & all))
+            return vmas_aux::fail(VMAS_E_INVALID, "vmas_mpe_outputs: a team is empty");
+        for (int m : {io->sum_mode_good, io->sum_mode_adv})
+            if (m < 1 || m > VMAS_MPE_MAX_AGENTS || (m & (m - 1)))
+                return vmas_aux::fail(VMAS_E_INVALID, "vmas_mpe_outputs: sum mode %d", m);
+    }
+    for (int l = 0; l < nl; ++l)
+        if (!io->landmark_pos[l].p) return vmas_aux::fail(VMAS_E_INVALID, "vmas_mpe_outputs: null pointer (landmark %d)", l);
+    int w_max = 0;
+    for (int i = 0; i < n; ++i) {
+        if (!io->pos[i].p || (rew && (!io->rewards[i] || (io->task == VMAS_MPE_TAG && !io->agent_rew[i]))) ||
+            (obs && (!io->vel[i].p || !io->obs[i])))
+            return vmas_aux::fail(VMAS_E_INVALID, "vmas_mpe_outputs: null pointer (agent %d)", i);
+        if (!obs) continue;
+        const int nt = io->n_terms[i];
+        if (nt < 1 || nt > VMAS_MPE_MAX_TERMS) return vmas_aux::fail(VMAS_E_INVALID, "vmas_mpe_outputs: term count (agent %d)", i);
+        for (int t = 0; t < nt; ++t) {
+            const VmasMpeTerm q = io->terms[i][t];
+            const bool ok = q.kind == VMAS_MPE_SELF_VEL || q.kind == VMAS_MPE_SELF_POS ||
+                            (q.kind == VMAS_MPE_REL_LANDMARK && q.index < nl) ||
+                            ((q.kind == VMAS_MPE_REL_AGENT || q.kind == VMAS_MPE_AGENT_VEL) && q.index < n);
+            if (!ok) return vmas_aux::fail(VMAS_E_INVALID, "vmas_mpe_outputs: term %d of agent %d", t, i);
+        }
+        w_max = 2 * nt > w_max ? 2 * nt : w_max;
+    }
+    if (device < 0) {
+        if (io->out_delta) return vmas_aux::fail(VMAS_E_INVALID, "vmas_mpe_outputs: out_delta on the host");
+        for (long b = 0; b < io->batch; ++b) {
+            if (rew) {
+                if (io->task == VMAS_MPE_SPREAD)
+                    vmas_mpe::spread_reward(*io, b, 0);
+                else
+                    vmas_mpe::tag_reward(*io, b, 0);
+            }
+            if (obs)
+                for (int k = 0; k < n; ++k) vmas_mpe::obs_row(*io, b, k, io->obs[k] + b * 2 * io->n_terms[k]);
+        }
+        return VMAS_OK;
+    }
+    VMAS_AUX_HIP(hipSetDevice(device));
+    hipLaunchKernelGGL(k_mpe, dim3((io->batch + 255) / 256), dim3(256), (size_t)4 * 64 * w_max * sizeof(float),
+                       (hipStream_t)stream, *io, w_max);
     VMAS_AUX_HIP(hipGetLastError());
     return VMAS_OK;
 }

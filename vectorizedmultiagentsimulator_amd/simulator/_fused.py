@@ -158,7 +158,8 @@ def ray_target(world, e, keep: list, dev) -> "N.VmasRayTarget":
 def direct_outputs(world, specs):
     """The step outputs of one fused launch during a graph-mode capture (StepGraph's
     DirectOutputs): ``specs`` per category (obs, rewards, done) None or (dtype, member shape, n
-    members).  Returns (the launch's out_delta address, per category its n member tensors -- views
+    members) -- or (dtype, [each member's shape], None) for members of different shapes.
+    Returns (the launch's out_delta address, per category its member tensors -- views
     of one buffer whose replays the graph relocates to fresh tensors -- or None).  Outside a
     capture (None, [None, None, None]): the scenario allocates its outputs as before."""
     d = getattr(world, "_direct_out", None)

@@ -134,10 +134,11 @@ _STEP_METHODS = ("reward", "observation", "done", "info", "pre_step", "post_step
 # The scenarios whose step code the replay trusts beyond the watched eager step (write-only
 # attributes, direct outputs): the four benchmark scenarios, each held to its eager step by
 # tests/test_graph.py, navigation, held to it by tests/test_navigation_gpu.py, and sampling, held to
-# it by tests/test_sampling_gpu.py (not
+# it by tests/test_sampling_gpu.py, wheel and dispersion (tests/test_wheel_dispersion_gpu.py) and the
+# two MPE scenarios (tests/test_step_graph_mpe_gpu.py), as paths relative to the scenarios directory (not
 # every file of the scenarios directory -- the debug scenarios are replayed like a user's scenario).
 _TRUSTED_FILES = ("balance.py", "transport.py", "discovery.py", "flocking.py", "navigation.py", "sampling.py",
-                  "wheel.py", "dispersion.py")
+                  "wheel.py", "dispersion.py", "mpe/simple_spread.py", "mpe/simple_tag.py")
 
 
 def _trusted_scenario(scenario) -> bool:
@@ -145,7 +146,7 @@ def _trusted_scenario(scenario) -> bool:
         return False
     f = os.path.abspath(type(scenario).make_world.__code__.co_filename)
     scn_dir = os.path.join(os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))), "scenarios")
-    return os.path.dirname(f) == scn_dir and os.path.basename(f) in _TRUSTED_FILES
+    return os.path.relpath(f, scn_dir).replace(os.sep, "/") in _TRUSTED_FILES
 
 
 def _write_only(o, k: str, scn_cls=None) -> bool:
@@ -548,9 +549,11 @@ class DirectOutputs:
                 out.append(None)
                 continue
             dt, shape, n = spec
-            numel = n * int(np.prod(shape, dtype=np.int64))
-            buf = torch.empty(numel * torch.empty((), dtype=dt).element_size(), dtype=torch.uint8, device=self.dev)
-            members = list(buf.view(dt).view(n, *shape).unbind(0))
+            # (n None: `shape` lists the members' shapes -- rows of different widths, one after the other)
+            shapes = [tuple(sh) for sh in shape] if n is None else [tuple(shape)] * n
+            sizes = [int(np.prod(sh, dtype=np.int64)) for sh in shapes]
+            buf = torch.empty(sum(sizes) * torch.empty((), dtype=dt).element_size(), dtype=torch.uint8, device=self.dev)
+            members = [m.view(sh) for m, sh in zip(buf.view(dt).split(sizes), shapes)]
             self.regions.append({"buf": buf, "dtype": dt, "members": members,
                                  "word": self.words.data_ptr() + 8 * (3 * k + c)})
             out.append(members)
